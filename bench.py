@@ -1,8 +1,16 @@
 """Benchmark: Qwen3-TTS-12Hz-1.7B CustomVoice, batch 8 x 200-token prompts, streaming-text decode
 (BASELINE.json configs[2]) on the MI355X HIP path.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step).  `--full` adds every
+other figure, each measured in runs of its own after the timed steps: batch 1, first-packet latencies, the kernel
+table and rooflines (`--roofline 0` leaves them out) and the CPU baseline (`--cpu-baseline 0` leaves it out).
+`--dump-outputs DIR` writes what the last timed step returned to its caller, per utterance i of the batch:
+DIR/codes_<i>.npy (frames x code groups) and DIR/pcm_<i>.npy (24 kHz PCM), float32 (`r<rank>_` in front with more
+than one rank).  Weights, token ids and the sampling seed of every step are fixed, so two runs with the same arguments
+see the same inputs.
 
 `--gpus N` (N > 1) without a launcher starts the N ranks itself (torch.distributed.run in a child process, before
 this process makes any GPU call); under a launcher WORLD_SIZE must equal N.  Ranks talk over RCCL ("nccl").
@@ -600,7 +608,15 @@ def main():
                     help="cv8: configs[2] (default, weak scaling: 8 x 200-token CustomVoice utterances per GPU); vd64: "
                          "configs[3] (strong scaling: 64 mixed-length VoiceDesign requests LPT-sharded over the ranks)")
     ap.add_argument("--slots", type=int, default=64, help="vd64: continuously refilled batch rows per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure batch 1, first-packet latencies, the kernel table and "
+                         "rooflines (--roofline) and the CPU baseline (--cpu-baseline); a plain run prints the headline "
+                         "figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's codes and PCM of every utterance to DIR/<name>.npy (float32)")
     a = ap.parse_args()
+    if a.dump_outputs and a.workload != "cv8":
+        ap.error("--dump-outputs is implemented for the default workload (cv8)")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a.gpus))  # before any GPU call: the N ranks run in child processes
     world, rank, local, backend, dist, dev = init_ranks(a)
@@ -629,7 +645,10 @@ def main():
         codes, _ = tts.model.generate(input_ids=ids[:n], languages=langs[:n], speakers=spk[:n], non_streaming_mode=False,
                                       seed=seed, **gen)
         wavs, sr = tts.model.speech_tokenizer.decode([{"audio_codes": c} for c in codes])
+        last["codes"], last["wavs"] = codes, wavs  # what the caller receives (kept for --dump-outputs)
         return sum(w.shape[0] for w in wavs) / sr, time.perf_counter() - t0
+
+    last = {}
 
     for i in range(a.warmup):
         step(100 + i)
@@ -653,6 +672,49 @@ def main():
         from qwen_tts.dp import reduce_timing
         dt, audio = reduce_timing(dt, audio, device=dev)
     value = audio / dt
+    if a.dump_outputs and a.steps > 0:
+        dump_outputs(a.dump_outputs, last["codes"], last["wavs"], world, rank)
+    if rank == 0:
+        per_utt_rtf = value / (B * world)
+        from qwen_tts import _hip
+        out = {"metric": "audio-seconds/sec (RTF) + p50 first-packet latency, 1.7B @ batch 1/8, 1->8 GPU",
+               "value": round(value, 3), "unit": "audio-seconds/sec", "n_gpus": world, "steps": a.steps,
+               "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 2), "higher_is_better": True,
+               "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic (seeded weights + token ids)",
+               "config": {"workload": f"Qwen3-TTS-12Hz-{a.preset} B={B}/GPU x {a.prompt_tokens}-token prompts, "
+                                      f"streaming text, {a.frames} frames + codec decode",
+                          "global_batch": B * world, "seq_len": a.prompt_tokens, "frames": a.frames,
+                          "parallelism": f"dp{world}"},
+               "rtf_per_utterance": round(per_utt_rtf, 2),
+               "full_batch_latency_p50_ms": round(1e3 * float(np.median(lat)), 1), "full": a.full,
+               "build_id": _hip.BUILD_ID, "dist_backend": backend if world > 1 else None,
+               "rccl_ranks": world if backend == "nccl" and world > 1 else 0,
+               "per_rank_value": [round(v, 3) for v in per_rank],
+               "launcher": os.environ.get("QT_BENCH_LAUNCHER", "external" if world > 1 else None)}
+    if a.full:
+        extra = full_figures(a, tts, cfg, step, ids, spk, langs, gen, B, world, rank)
+        if rank == 0:
+            out.update(extra)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def dump_outputs(d, codes, wavs, world, rank):
+    """--dump-outputs: the codes and PCM the last timed step returned, one float32 .npy per utterance (codec codes are
+    small integers, exact in float32); B = 8 x 256 frames is ~16 MB."""
+    os.makedirs(d, exist_ok=True)
+    pre = f"r{rank}_" if world > 1 else ""
+    for i, (c, w) in enumerate(zip(codes, wavs)):
+        np.save(os.path.join(d, f"{pre}codes_{i}.npy"), torch.as_tensor(c).cpu().numpy().astype(np.float32))
+        np.save(os.path.join(d, f"{pre}pcm_{i}.npy"), np.asarray(w, dtype=np.float32))
+
+
+def full_figures(a, tts, cfg, step, ids, spk, langs, gen, B, world, rank):
+    """--full: everything the result line holds beyond the headline figures, measured after the timed steps in runs of
+    their own (every rank takes the first-packet samples, as its own batch's; rank 0 does the rest).  Returns the extra
+    keys of the JSON line."""
     # talker cache length at the end of a timed step (prompt + frames), before other shapes reuse the sessions
     L_end = max(int(ss.meta["kv_pos"].max().item()) for ss in tts.model.engine.all_sessions() if ss.B == B)
     fr = whole_frame_roofline(tts, cfg, B) if a.roofline and rank == 0 else None
@@ -685,7 +747,6 @@ def main():
         first_packet(n)
         fp[n] = 1e3 * float(np.median([first_packet(n) for _ in range(9)]))
     roof = table = frame_roof = pf_roof = gateup = None
-    from qwen_tts import _hip
     if a.roofline and rank == 0 and eng_wdt_bf16(tts):
         # decode attention at the run's mean cache length (prompt + half the frames)
         L_mean = max(L_end - a.frames // 2, 1)
@@ -740,28 +801,9 @@ def main():
         # 8 threads: the reference's own published CPU figure and the cross-check use 8 (the box's CPU
         # share is 16, os.cpu_count() reports the whole host)
         cpu = cpu_baseline(B, a.prompt_tokens, a.cpu_frames, a.cpu_threads, a.preset)
-    if rank == 0:
-        per_utt_rtf = value / (B * world)
-        out = {"metric": "audio-seconds/sec (RTF) + p50 first-packet latency, 1.7B @ batch 1/8, 1->8 GPU",
-               "value": round(value, 3), "unit": "audio-seconds/sec", "n_gpus": world, "steps": a.steps,
-               "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 2), "higher_is_better": True,
-               "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic (seeded weights + token ids)",
-               "config": {"workload": f"Qwen3-TTS-12Hz-{a.preset} B={B}/GPU x {a.prompt_tokens}-token prompts, "
-                                      f"streaming text, {a.frames} frames + codec decode",
-                          "global_batch": B * world, "seq_len": a.prompt_tokens, "frames": a.frames,
-                          "parallelism": f"dp{world}"},
-               "rtf_per_utterance": round(per_utt_rtf, 2), "batch1": b1,
-               "first_packet_p50_ms": round(fp[B], 1), "first_packet_p50_ms_b1": round(fp[1], 1),
-               "full_batch_latency_p50_ms": round(1e3 * float(np.median(lat)), 1),
-               "roofline": roof, "frame_roofline": frame_roof, "kernel_table": table, "gateup_roofline": gateup,
-               "prefill_mfma": pf_roof, "cpu_baseline": cpu, "build_id": _hip.BUILD_ID,
-               "dist_backend": backend if world > 1 else None,
-               "rccl_ranks": world if backend == "nccl" and world > 1 else 0,
-               "per_rank_value": [round(v, 3) for v in per_rank],
-               "launcher": os.environ.get("QT_BENCH_LAUNCHER", "external" if world > 1 else None)}
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
+    return {"batch1": b1, "first_packet_p50_ms": round(fp[B], 1), "first_packet_p50_ms_b1": round(fp[1], 1),
+            "roofline": roof, "frame_roofline": frame_roof, "kernel_table": table, "gateup_roofline": gateup,
+            "prefill_mfma": pf_roof, "cpu_baseline": cpu}
 
 
 def vd64_requests(n=64, seed=4321):

@@ -8,4 +8,4 @@ timeout -k 10 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out/p
 timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc2 -o run -- python3 tools/pmc_gateup.py > gpurun_out/pmc2.log 2>&1
 python3 tools/pmc_reduce.py gpurun_out/pmc1 gpurun_out/pmc2 > profiles/r01_pmc_gateup.json
 cp profiles/r01_pmc_gateup.json gpurun_out/
-bash tools/prof.sh r01bench
+bash tools/prof.sh r01bench --full

@@ -2,6 +2,8 @@
 # talker gate-up GEMV), copied into profiles/ on the box so the bench line's traffic is this build's, then the bench
 # line and the rocprofv3 kernel-trace stats of the same bench command.  Each GPU step time-limited, chained (set -e).
 set -e
+OUT=${OUT:-bench_out}  # where the logs go
+mkdir -p "$OUT"
 mkdir -p gpurun_out
 root=$(pwd)
 cd /tmp && export TMPDIR=/tmp && cd "$root"
@@ -15,9 +17,9 @@ timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d gpurun_out
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc2 -o run -- python3 tools/pmc_gateup.py > gpurun_out/pmc2.log 2>&1
 python3 tools/pmc_reduce.py gpurun_out/pmc1 gpurun_out/pmc2 "$(cat gpurun_out/pmc_build_id.txt)" > gpurun_out/r04c_pmc_gateup.json
 cp gpurun_out/r04c_pmc_*.json profiles/
-timeout -k 10 600 python bench.py > gpurun_out/r04c_bench.log 2>&1
-tail -1 gpurun_out/r04c_bench.log > gpurun_out/r04c_bench_line.json
-bash tools/prof.sh r04cprof --cpu-baseline 0
+timeout -k 10 600 python bench.py --full > $OUT/r04c_bench.log 2>&1
+tail -1 $OUT/r04c_bench.log > $OUT/r04c_bench_line.json
+bash tools/prof.sh r04cprof --full --cpu-baseline 0
 # the roofline kernels' average durations in that trace, labelled with the build (bench.py attaches them by build id)
 bid=$(cat gpurun_out/pmc_build_id.txt)
 python3 tools/rocprof_kernel_avg.py gpurun_out/r04cprof/run_kernel_stats.csv attn_oproj_hs_k $bid > gpurun_out/r04c_rocprof_attn_oproj_hs.json
