@@ -10,6 +10,14 @@
   (measured: 100% / 99.1% tiny, 100% / 97.4% 1.7B dims).
 * Speaker encoder: log-mel |diff| <= 1e-3, x-vector relative L2 error <= 1e-3 (fp32), <= 5e-2 (bf16).
 * End to end: create_voice_clone_prompt / generate_voice_clone on the tiny Base preset.
+* Kernel units in the layouts the product uses (strided, bf16, T < 8; references in tests/small_kernel_refs.py):
+  fp32 results within max(2 x plain torch fp32's error against fp64, 4 fp32 ulp), bf16 results within one bf16 step
+  of the rounded fp64 result and equal on >= 99.9 %, moves exact.
+  measured (kernel vs fp64 / torch-fp32 vs fp64, scaled as small_kernel_refs.py describes): layernorm 0 .. 2.1e-7 /
+  0 .. 2.1e-7 (mean-1e3 row 1.1e-5 / 1.1e-5) of the row's largest |ref|; time_stats mean 0 .. 2.2e-7 / 0 .. 2.4e-7,
+  std 5e-10 .. 1.2e-7 / 5e-10 .. 1.3e-7 of the case's largest |ref| (some cases up to 2.5 x torch's error, all
+  inside the 4-ulp floor); scale_add 3.3e-8 .. 5.7e-8 / 5.3e-8 .. 8.0e-8 of |x s| + |res|; bf16 layernorm and
+  scale_add meet the cap (plain fp32 on CPU: equal everywhere).
 """
 import os
 
@@ -193,8 +201,171 @@ def test_time_stats_and_mel():
     torch.testing.assert_close(out.cpu(), torch.log(torch.clamp(mag @ basis.T, min=1e-5)), atol=1e-5, rtol=1e-5)
 
 
+# ------------------------------------------------------------------------------------------ kernels, as the product calls them
+# Non-default leading dimensions into sentinel-filled wider buffers, bf16, the shapes around the wave / block sizes.
+# fp32 results: within max(2 x the error of plain torch fp32, 4 fp32 ulp) of the fp64 reference; bf16 results: within
+# one bf16 step of it, equal on >= 99.9 %; pure moves: exact (tests/small_kernel_refs.py).
+F32, BF16 = torch.float32, torch.bfloat16
+SENT = 7.0
+
+
+def _sent(shape, dtype, dev):
+    return torch.full(shape, SENT, dtype=dtype, device=dev)
+
+
+def _is_sent(t):
+    return bool((t == SENT).all())
+
+
+def _fp32_ok(what, got, plain32, ref64, scale, per_row=False):
+    import small_kernel_refs as R
+    ok, ek, et = R.judge_fp32(got, plain32, ref64, scale, per_row)
+    print(f"{what}: kernel vs fp64 {ek:.3g}, torch-fp32 vs fp64 {et:.3g}")
+    assert ok, (what, ek, et)
+
+
+@pytest.mark.parametrize("o_dtype", [F32, BF16])
+@pytest.mark.parametrize("M,N", [(1, 1), (2, 257), (37, 64), (5, 512)])
+def test_layernorm_strided(M, N, o_dtype):
+    """ldx = N + 3, ldo = N + 5.  fp32 output: the last row has mean 1e3 and spread ~1, which the kernel's two-pass
+    form survives (a one-pass form does not: tests/test_small_kernel_refs.py)."""
+    import small_kernel_refs as R
+    from qwen_tts import kernels as Kn
+    dev = _dev()
+    x, w, b = R.layernorm_inputs(M, N, o_dtype == F32)
+    xb = _sent((M, N + 3), F32, dev)
+    xb[:, :N] = x.to(dev)
+    out = _sent((M + 1, N + 5), o_dtype, dev)
+    Kn.layernorm(xb, w.to(dev), b.to(dev), R.LAYERNORM_EPS, out, M, N, ldx=N + 3, ldo=N + 5)
+    assert _is_sent(out[:M, N:]) and _is_sent(out[M:]) and _is_sent(xb[:, N:])
+    got, ref = out[:M, :N].cpu(), R.layernorm(x, w, b, R.LAYERNORM_EPS)
+    if o_dtype == F32:
+        _fp32_ok(f"layernorm {M}x{N}", got, R.layernorm(x, w, b, R.LAYERNORM_EPS, F32), ref, R.row_scale(ref), per_row=True)
+    else:
+        R.assert_bf16_cap(got, ref, f"layernorm {M}x{N}")
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("C", [5, 64, 70, 128])
+@pytest.mark.parametrize("T", [1, 3, 8, 9, 37])
+def test_time_stats_pooling_layout(T, C, dtype):
+    """The speaker encoder's layout: x the first C columns of [B][T][3C], logits with ldl = C, mean / std the two
+    halves of [B][2C].  T < 8 leaves some of the kernel's 8 time slices empty; channel 1 is constant in time (the
+    eps floor decides its std); logits span +-30 (the online softmax rescales)."""
+    import small_kernel_refs as R
+    from qwen_tts import kernels as Kn
+    dev = _dev()
+    B = 2
+    x, lg = R.time_stats_inputs(B, T, C, dtype)
+    xb = _sent((B, T, 3 * C), dtype, dev)
+    xb[:, :, :C] = x.to(dev)
+    for logits in (None, lg):
+        ms = _sent((B + 1, 2 * C), F32, dev)
+        Kn.time_stats(xb, B, T, C, ms, ms[:, C:], logits=None if logits is None else logits.to(dev), ldx=3 * C, ldl=C,
+                      ld_out=2 * C)
+        assert _is_sent(ms[B:])
+        ref = R.time_stats(x, logits)
+        plain = R.time_stats(x, logits, dtype=F32)
+        for i, name in enumerate(("mean", "std")):
+            _fp32_ok(f"time_stats {name} T={T} C={C} logits={logits is not None}", ms[:B, i * C:(i + 1) * C].cpu(),
+                     plain[i], ref[i], ref[i].abs().max())
+        mean_only = _sent((B + 1, 2 * C), F32, dev)  # std_out omitted: the second half stays untouched
+        Kn.time_stats(xb, B, T, C, mean_only, None, logits=None if logits is None else logits.to(dev), ldx=3 * C,
+                      ldl=C, ld_out=2 * C)
+        assert torch.equal(mean_only[:B, :C], ms[:B, :C]) and _is_sent(mean_only[:, C:]) and _is_sent(mean_only[B:])
+    assert _is_sent(xb[:, :, C:])
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("B,T,C", [(2, 5, 1), (3, 10, 6), (2, 9, 70)])  # B*T*C = 10, 180, 1260: no multiple of 256
+def test_scale_add_strided(B, T, C, dtype):
+    import small_kernel_refs as R
+    from qwen_tts import kernels as Kn
+    dev = _dev()
+    x, s, res = R.scale_add_inputs(B, T, C, dtype)
+    xb, rb = _sent((B * T, C + 2), dtype, dev), _sent((B * T, C + 4), dtype, dev)
+    sb = _sent((B, C + 1), F32, dev)
+    xb[:, :C], rb[:, :C], sb[:, :C] = x.view(B * T, C).to(dev), res.view(B * T, C).to(dev), s.to(dev)
+    out = _sent((B * T + 1, C + 3), dtype, dev)
+    Kn.scale_add(xb, sb, rb, B, T, C, out, ldx=C + 2, lds=C + 1, ldr=C + 4, ldo=C + 3)
+    assert _is_sent(out[:B * T, C:]) and _is_sent(out[B * T:])
+    got, ref = out[:B * T, :C].view(B, T, C).cpu(), R.scale_add(x, s, res)
+    if dtype == F32:
+        scale = (x.double() * s.double()[:, None]).abs() + res.double().abs()
+        _fp32_ok(f"scale_add {B}x{T}x{C}", got, R.scale_add(x, s, res, F32), ref, scale)
+    else:
+        R.assert_bf16_cap(got, ref, f"scale_add {B}x{T}x{C}")
+
+
+@pytest.mark.parametrize("o_dtype", [F32, BF16])
+@pytest.mark.parametrize("B,T,W", [(2, 5, 1), (3, 10, 8), (2, 9, 70)])
+def test_bcast_rows_strided(B, T, W, o_dtype):
+    from qwen_tts import kernels as Kn
+    dev = _dev()
+    g = torch.Generator().manual_seed(W)
+    v = torch.randn(B, W, generator=g).to(BF16).float()  # bf16-exact values: the bf16 output is a pure move too
+    vb = _sent((B, W + 2), F32, dev)
+    vb[:, :W] = v.to(dev)
+    out = _sent((B * T + 1, W + 4), o_dtype, dev)
+    Kn.bcast_rows(vb, B, T, W, out[:, 3:], ldv=W + 2, ldo=W + 4)  # into a strided slice, as speaker.py does
+    assert torch.equal(out[:B * T, 3:3 + W].view(B, T, W).cpu(), v[:, None, :].expand(B, T, W).to(o_dtype))
+    assert _is_sent(out[:B * T, :3]) and _is_sent(out[:B * T, 3 + W:]) and _is_sent(out[B * T:])
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("B,Tp,v,C", [(2, 5, 2, 1), (3, 10, 7, 6), (2, 9, 0, 70), (2, 4, 4, 3)])
+def test_zero_tail_strided(B, Tp, v, C, dtype):
+    from qwen_tts import kernels as Kn
+    dev = _dev()
+    g = torch.Generator().manual_seed(C)
+    x = (torch.randn(B, Tp, C + 3, generator=g) + 3).to(dtype)  # no zeros in the input
+    y = x.to(dev)
+    Kn.zero_tail(y, B, Tp, v, C, ldx=C + 3)
+    ref = x.clone()
+    ref[:, v:, :C] = 0
+    assert torch.equal(y.cpu(), ref)
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("B,T,C,l,r", [(2, 9, 1, 3, 2), (2, 9, 5, 8, 8), (3, 7, 70, 0, 6)])
+def test_pad_time_strided_exact(B, T, C, l, r, dtype, mode):
+    """Without x2 a pure move: exact in both dtypes.  ldx = C + 2, ldo = C + 3; (9, 8, 8): reflect at its limit
+    left = right = T - 1."""
+    from qwen_tts import kernels as Kn
+    dev = _dev()
+    g = torch.Generator().manual_seed(mode + C)
+    x = torch.randn(B, T, C, generator=g).to(dtype)
+    xb = _sent((B * T, C + 2), dtype, dev)
+    xb[:, :C] = x.view(B * T, C).to(dev)
+    tt = T + l + r + 2
+    out = _sent((B * tt + 1, C + 3), dtype, dev)
+    Kn.pad_time(xb, B, T, C, l, r, mode, out, t_total=tt, ldx=C + 2, ldo=C + 3)
+    pm = {0: "constant", 1: "reflect", 2: "replicate"}[mode]
+    ref = F.pad(x.float().transpose(1, 2), (l, r), mode=pm).transpose(1, 2)
+    ref = torch.cat([ref, torch.zeros(B, 2, C)], 1).to(dtype)
+    assert torch.equal(out[:B * tt, :C].view(B, tt, C).cpu(), ref)
+    assert _is_sent(out[:B * tt, C:]) and _is_sent(out[B * tt:])
+
+
+def test_pad_time_reflect_limit():
+    from qwen_tts import kernels as Kn
+    dev = _dev()
+    B, T, C = 2, 6, 4
+    x = torch.randn(B, T, C, generator=torch.Generator().manual_seed(3)).to(dev)
+    for l, r in ((T, 0), (0, T)):
+        out = _sent((B, 2 * T + 2, C), F32, dev)
+        with pytest.raises(RuntimeError):
+            Kn.pad_time(x, B, T, C, l, r, 1, out)
+        torch.cuda.synchronize()
+        assert _is_sent(out)
+    out = _sent((B, 2 * T - 1, C), F32, dev)
+    Kn.pad_time(x, B, T, C, T - 1, 0, 1, out)
+    assert torch.equal(out, torch.cat([x.flip(1)[:, :-1], x], 1))
+
+
 # ------------------------------------------------------------------------------------------ golden (reference)
-CASES = [("tiny-base", "tiny", "frontend_tiny.npz"), ("1.7b-base", "full", "frontend_full.npz")]
+CASES =[("tiny-base", "tiny", "frontend_tiny.npz"), ("1.7b-base", "full", "frontend_full.npz")]
 
 
 def _encoder(preset, dtype):

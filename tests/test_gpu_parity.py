@@ -1537,6 +1537,7 @@ def test_prefill_buffers_lru_bounded(tiny_models):
     """Static prefill buffers are kept for the PREFILL_CACHE most recently used prompt lengths only (LRU): a server
     seeing many distinct prompt lengths does not grow HBM without bound, and evicted / re-created lengths still
     decode exactly as before."""
+    import gc
     from cases import talker_cases
     from qwen_tts import talker as T
     from qwen_tts.model import TTSModel
@@ -1553,6 +1554,9 @@ def test_prefill_buffers_lru_bounded(tiny_models):
                 else:
                     assert all(torch.equal(a, b) for a, b in zip(c, first[n])), n
             torch.cuda.synchronize()
+            # unreachable cycles left by earlier tests (a dropped model's buffers) die whenever the collector next
+            # runs, which may be between two of these readings: collect first, so only reachable memory is counted
+            gc.collect()
             mem.append(torch.cuda.memory_allocated())
         for s in model.engine.all_sessions():
             assert len(s.prefill) <= T.PREFILL_CACHE
