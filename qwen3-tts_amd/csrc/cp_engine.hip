@@ -1022,7 +1022,8 @@ extern "C" int qt_cp_step(const qt_cp_step_args* a, void* stream) {
 // qt_cp_step with the previous step's token choice at its start (qt_cp_step_sampled, include/qwen3tts_amd.h)
 extern "C" int qt_cp_step_sampled(const qt_cp_step_args* a, const qt_sample_args* sa, void* stream) {
   if (!a || !sa || sa->R != a->R || sa->V <= 0 || sa->V > 2048 || !sa->tok_out || !sa->logits) return QT_ERR_SHAPE;
-  if (sa->do_sample && sa->top_k > sa->V) return QT_ERR_ARG;
+  if (!sa->rows && sa->do_sample && sa->top_k > sa->V) return QT_ERR_ARG;
+  if (sa->rows && ((unsigned long long)sa->rows & 15)) return QT_ERR_ARG;
   if (sa->ctr_stride < 0 || (sa->force && (!sa->pick || !sa->codes))) return QT_ERR_ARG;
   if (!sa->emb_table || sa->emb_dim != H || !sa->emb2_table || sa->emb2_dim != (NQ + 2 * NKV) * D) return QT_ERR_SHAPE;
   qt_cp_step_args b = *a;  // qkv0 / x come from the sampler's rows: any non-null pointer passes the checks

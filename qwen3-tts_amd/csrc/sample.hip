@@ -31,7 +31,8 @@ __global__ __launch_bounds__(NT) void sample_k(SK pk) {
 
 extern "C" int qt_sample(const qt_sample_args* a, void* stream) {
   if (!a || a->R <= 0 || a->V <= 0 || a->V > NT * 16 || !a->tok_out) return QT_ERR_SHAPE;
-  if (a->do_sample && a->top_k > a->V) return QT_ERR_ARG;
+  if (!a->rows && a->do_sample && a->top_k > a->V) return QT_ERR_ARG;
+  if (a->rows && ((unsigned long long)a->rows & 15)) return QT_ERR_ARG;
   if (a->ctr_stride < 0) return QT_ERR_SHAPE;
   if (a->emb_table && (!a->emb_out || a->emb_dim % 4 || a->emb_ld % 4)) return QT_ERR_SHAPE;
   if (a->emb_out16 && (!a->emb_table || a->emb_ld16 % 4)) return QT_ERR_SHAPE;
@@ -45,3 +46,6 @@ extern "C" int qt_sample(const qt_sample_args* a, void* stream) {
   else hipLaunchKernelGGL(sample_k<16>, dim3(a->R), dim3(NT), 0, st, k);
   return hipGetLastError() == hipSuccess ? 0 : QT_ERR_LAUNCH;
 }
+
+extern "C" long long qt_sample_row_bytes(void) { return (long long)sizeof(qt_sample_row); }
+extern "C" long long qt_sample_args_bytes(void) { return (long long)sizeof(qt_sample_args); }

@@ -128,8 +128,15 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
   // indices, the seen flags and the device counters through always-valid pointers (the logits row stands in
   // when an optional pointer is null), selected afterwards -- a per-element or per-pointer branch made the
   // compiler wait for each load in turn (one L2 round trip each).
-  const bool pen = p.seen && p.rep_penalty != 1.0f;
-  const unsigned char* sr = pen ? p.seen + (long long)r * V : (const unsigned char*)lg;
+  // Per-row parameters (p.rows): the row's 32-byte record joins the same group of loads -- the 16-byte-aligned
+  // start of the logits row stands in without a table -- and its values are broadcast from the first lane, so every
+  // branch on them is a scalar one, as on the kernel arguments they replace (every thread of the row reads the same
+  // record: block-uniform, which the barrier count relies on).  The seen flags are loaded whenever a table is given,
+  // since whether the row's penalty is 1 is known only once the record has arrived.
+  const bool pr = p.rows != nullptr;
+  const u32x4_t* rwp = pr ? (const u32x4_t*)(p.rows + r) : (const u32x4_t*)((unsigned long long)lg & ~15ull);
+  const bool pen_ld = p.seen && (pr || p.rep_penalty != 1.0f);
+  const unsigned char* sr = pen_ld ? p.seen + (long long)r * V : (const unsigned char*)lg;
   const int* ngp = p.n_generated ? p.n_generated + r * p.ctr_stride : (const int*)lg;
   const int* stpp = p.step ? p.step + r * p.ctr_stride : (const int*)lg;
   const int* prp = p.philox_row ? p.philox_row + r : (const int*)lg;
@@ -137,6 +144,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
   const unsigned long long* sdp = p.seed_ptr ? p.seed_ptr : (const unsigned long long*)lg;
   float s[PER];
   unsigned char sn[PER];
+  const u32x4_t rw0 = rwp[0], rw1 = rwp[1];
 #pragma unroll
   for (int j = 0; j < PER; ++j) s[j] = lg[min(tid + j * NT, V - 1)];
 #pragma unroll
@@ -149,14 +157,22 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
   const int ngen = p.n_generated ? ngr : 1 << 30;
   const unsigned stp = p.step ? (unsigned)str : 0u;
   const int finv = p.finished ? fnr : 0;
-  const unsigned long long seed = p.seed_ptr ? sdv : p.seed;
+  const auto uni = [](unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); };
+  const float temperature = pr ? __uint_as_float(uni(rw0[0])) : p.temperature;
+  const float top_p = pr ? __uint_as_float(uni(rw0[1])) : p.top_p;
+  const float rep_penalty = pr ? __uint_as_float(uni(rw0[2])) : p.rep_penalty;
+  const int top_k = pr ? (int)uni(rw0[3]) : p.top_k;
+  const int do_sample = pr ? (int)uni(rw1[0]) : p.do_sample;
+  const unsigned long long seed =
+      pr ? ((unsigned long long)uni(rw1[3]) << 32 | uni(rw1[2])) : p.seed_ptr ? sdv : p.seed;
+  const bool pen = p.seen && rep_penalty != 1.0f;
   const unsigned prow = p.philox_row ? (unsigned)prr : (unsigned)(p.row_base + r);  // Philox stream id
   const bool eos_mask = p.eos_id >= 0 && (ngen < p.min_new_tokens || p.ignore_eos);
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
     const int v = tid + j * NT;
     float x = s[j];
-    if (pen && sn[j]) x = x < 0.f ? x * p.rep_penalty : x / p.rep_penalty;
+    if (pen && sn[j]) x = x < 0.f ? x * rep_penalty : x / rep_penalty;
     if ((eos_mask && v == p.eos_id) || (v >= p.suppress_lo && v < p.suppress_hi && v != p.suppress_keep) || v >= V)
       x = -INFINITY;
     s[j] = x;
@@ -166,7 +182,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
     return -1;
   }
   int tok;
-  if (!p.do_sample) {
+  if (!do_sample) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
 #pragma unroll
@@ -187,7 +203,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
       if (sh[i] > best || (sh[i] == best && shi[i] < bi)) { best = sh[i]; bi = shi[i]; }
     tok = bi;
   } else {
-    const float invT = (p.temperature > 0.f && p.temperature != 1.0f) ? 1.0f / p.temperature : 1.0f;
+    const float invT = (temperature > 0.f && temperature != 1.0f) ? 1.0f / temperature : 1.0f;
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < PER; ++j) { s[j] *= invT; mx = fmaxf(mx, s[j]); }
@@ -202,7 +218,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
     // step, substep, row, token) -- an exact sample of softmax(s / T) restricted to the top-k set.  A wave left
     // with > 64 tied keys falls back to the block search.
     bool fast = false;
-    const bool fast_ok = p.top_k > 0 && p.top_k < V && p.top_k <= 64 && p.top_p >= 1.0f;
+    const bool fast_ok = top_k > 0 && top_k < V && top_k <= 64 && top_p >= 1.0f;
     // Histogram fast path (k <= 64, no top-p; p.algo 0 or 2): the k-th largest score located by a 256-bin value
     // histogram below the row maximum (bin = floor((max - s) * HB), HB bins per unit of s / T), then resolved exactly
     // among the boundary bin's scores; kept = {s >= k-th largest} (ties kept, TopKLogitsWarper).  Wave 0 then draws
@@ -236,19 +252,19 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
           if (lane >= o) scan += y;
         }
         const int excl = scan - loc;
-        const bool cross = excl < p.top_k && scan >= p.top_k;
+        const bool cross = excl < top_k && scan >= top_k;
         if (cross) {
           int c = excl, b = -1;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             if (b < 0) {
-              if (c + h[i] >= p.top_k) b = lane * 4 + i;
+              if (c + h[i] >= top_k) b = lane * 4 + i;
               else c += h[i];
             }
           }
           hb_s[0] = b; hb_s[1] = c;  // boundary bin, scores strictly above it
         }
-        if (lane == 63 && scan < p.top_k) hb_s[0] = -1;  // the top k reach below the histogram: fall through
+        if (lane == 63 && scan < top_k) hb_s[0] = -1;  // the top k reach below the histogram: fall through
       }
       bar();
       const int bs = hb_s[0];
@@ -266,7 +282,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
       if (bs >= 0 && hln_s[1] <= 64) {
         fast = true;
         if (w == 0) {
-          const int n0 = hln_s[0], n1 = hln_s[1], need = p.top_k - hb_s[1];  // 1 <= need <= n1
+          const int n0 = hln_s[0], n1 = hln_s[1], need = top_k - hb_s[1];  // 1 <= need <= n1
           const float mine = lane < n1 ? hl_s[1][lane] : -INFINITY;
           int gt = 0, ge = 0;
           for (int i = 0; i < n1; ++i) {
@@ -308,7 +324,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
       for (int j = 0; j < PER; ++j) nv += key[j] != 0u;
       int cw = wave_sum_i(nv);
       unsigned tw = 0u;
-      for (int bit = 30; bit >= 0 && cw > 64; bit -= 2) kth_step<PER>(key, p.top_k, bit, tw, cw);
+      for (int bit = 30; bit >= 0 && cw > 64; bit -= 2) kth_step<PER>(key, top_k, bit, tw, cw);
       int base = 0;
 #pragma unroll
       for (int j = 0; j < PER; ++j) {
@@ -339,7 +355,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
           }
           unsigned t = 0u;
           int cur = tot;
-          for (int bit = 30; bit >= 0 && cur > p.top_k; bit -= 2) kth_step<4>(ck, p.top_k, bit, t, cur);
+          for (int bit = 30; bit >= 0 && cur > top_k; bit -= 2) kth_step<4>(ck, top_k, bit, t, cur);
           if (lane == 0) tk_s = t;
         }
         const bool has = lane < nc_s[w];
@@ -385,12 +401,12 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
       if (mx == 1234.5f) p.tok_out[r] = 0;
       return -1;
     }
-    if (!fast && p.top_k > 0 && p.top_k < V) {
+    if (!fast && top_k > 0 && top_k < V) {
       // MSB-first construction of the k-th largest key, 2 bits per step.  Counts are per-thread VALU
       // compares summed by packed wave reductions (n1 | n2 << 16, n3) and one barrier per step; the search
       // stops as soon as exactly k keys are >= the prefix (that set is the top-k set).
       int cur = V, bit = 30;
-      for (; bit >= 0 && cur != p.top_k && cur > 256; bit -= 2) {
+      for (; bit >= 0 && cur != top_k && cur > 256; bit -= 2) {
         const unsigned c1 = tk | (1u << bit), c2 = tk | (2u << bit), c3 = tk | (3u << bit);
         int n12 = 0, n3 = 0;
 #pragma unroll
@@ -406,11 +422,11 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
         const int s12 = cnt3[buf][0][0] + cnt3[buf][0][1] + cnt3[buf][0][2] + cnt3[buf][0][3];
         const int t3 = cnt3[buf][1][0] + cnt3[buf][1][1] + cnt3[buf][1][2] + cnt3[buf][1][3];
         const int t1 = s12 & 0xFFFF, t2 = s12 >> 16;
-        if (t3 >= p.top_k) { tk = c3; cur = t3; }
-        else if (t2 >= p.top_k) { tk = c2; cur = t2; }
-        else if (t1 >= p.top_k) { tk = c1; cur = t1; }
+        if (t3 >= top_k) { tk = c3; cur = t3; }
+        else if (t2 >= top_k) { tk = c2; cur = t2; }
+        else if (t1 >= top_k) { tk = c1; cur = t1; }
       }
-      if (bit >= 0 && cur != p.top_k) {
+      if (bit >= 0 && cur != top_k) {
         // <= 256 keys remain >= tk: compact them into LDS and finish the search in wave 0, barrier-free
         if (tid == 0) ncand = 0;
         bar();
@@ -422,7 +438,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
           unsigned ck[4];
 #pragma unroll
           for (int i = 0; i < 4; ++i) ck[i] = lane + 64 * i < cur ? cand[lane + 64 * i] : 0u;
-          for (; bit >= 0 && cur != p.top_k; bit -= 2) {
+          for (; bit >= 0 && cur != top_k; bit -= 2) {
             const unsigned c1 = tk | (1u << bit), c2 = tk | (2u << bit), c3 = tk | (3u << bit);
             int n12 = 0, n3 = 0;
 #pragma unroll
@@ -432,9 +448,9 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
             }
             const int s12 = wave_sum_i(n12), t3 = wave_sum_i(n3);
             const int t1 = s12 & 0xFFFF, t2 = s12 >> 16;
-            if (t3 >= p.top_k) { tk = c3; cur = t3; }
-            else if (t2 >= p.top_k) { tk = c2; cur = t2; }
-            else if (t1 >= p.top_k) { tk = c1; cur = t1; }
+            if (t3 >= top_k) { tk = c3; cur = t3; }
+            else if (t2 >= top_k) { tk = c2; cur = t2; }
+            else if (t1 >= top_k) { tk = c1; cur = t1; }
           }
           if (lane == 0) shtk = tk;
         }
@@ -447,7 +463,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
       return -1;
     }
     if (!fast) {
-    if (p.top_p < 1.0f) {  // rare path: sorted list (descending) for the nucleus cut
+    if (top_p < 1.0f) {  // rare path: sorted list (descending) for the nucleus cut
       for (int j = 0; j < PER; ++j) {
         const int v = tid + j * NT;
         if (v < 4096) srt[v] = (v < V && okey(s[j]) >= tk) ? s[j] : -INFINITY;
@@ -473,7 +489,7 @@ QT_DEV int sample_row(const qt_sample_args& p, int stop, int r, int tid, SampSh&
         for (int j = 0; j < V && srt[j] > -INFINITY; ++j) tot += expf(srt[j] - mx);
         float cum = 0.f, cut = srt[0];
         for (int j = 0; j < V && srt[j] > -INFINITY; ++j) {
-          if (cum >= p.top_p * tot) break;
+          if (cum >= top_p * tot) break;
           cum += expf(srt[j] - mx);
           cut = srt[j];
         }

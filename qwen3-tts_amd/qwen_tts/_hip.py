@@ -97,6 +97,12 @@ class TalkerTailArgs(ctypes.Structure):
                 ("qkv", c_void_p), ("ldq", c_ll), ("ws", c_void_p), ("ws_bytes", c_ll), ("H", c_int), ("I", c_int)]
 
 
+class SampleRow(ctypes.Structure):
+    """qt_sample_row: one row's sampling parameters (32 bytes; records of a device table, SampleArgs.rows)"""
+    _fields_ = [("temperature", c_float), ("top_p", c_float), ("rep_penalty", c_float), ("top_k", c_int),
+                ("do_sample", c_int), ("reserved", c_int), ("seed", c_ull)]
+
+
 class SampleArgs(ctypes.Structure):
     _fields_ = [("logits", c_void_p), ("R", c_int), ("V", c_int), ("ld", c_ll), ("seen", c_void_p),
                 ("rep_penalty", c_float), ("n_generated", c_void_p), ("min_new_tokens", c_int), ("eos_id", c_int),
@@ -109,7 +115,7 @@ class SampleArgs(ctypes.Structure):
                 ("seed_ptr", c_void_p), ("debug_u", c_float), ("emb_out16", c_void_p), ("emb_ld16", c_ll),
                 ("emb2_table", c_void_p), ("emb2_dim", c_int), ("emb2_out", c_void_p), ("emb2_ld", c_ll),
                 ("algo", c_int), ("ctr_stride", c_int), ("philox_row", c_void_p), ("force", c_void_p),
-                ("pick", c_void_p)]
+                ("pick", c_void_p), ("rows", c_void_p)]
 
 
 EXPORTS = ["qt_gemm", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decode_attention", "qt_decode_attn_ws_bytes",
@@ -118,7 +124,7 @@ EXPORTS = ["qt_gemm", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decod
            "qt_cp_step", "qt_cp_prefill", "qt_cp_step_sampled", "qt_cp_step_ws_bytes", "qt_cp_step_supported", "qt_cp_step_dbg_bytes",
            "qt_talker_tail", "qt_talker_tail_ws_bytes", "qt_talker_tail_stamp_bytes", "qt_talker_tail_dbg_bytes",
            "qt_talker_tail_supported",
-           "qt_sample", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
+           "qt_sample", "qt_sample_row_bytes", "qt_sample_args_bytes", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
            "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
@@ -190,11 +196,12 @@ def load_library(path: str = LIB_PATH):
         "qt_time_stats": [P, c_int, c_ll, P, c_ll, c_int, c_int, c_int, c_float, P, P, c_ll, P],
         "qt_scale_add": [P, c_ll, P, c_ll, P, c_ll, c_int, c_int, c_int, c_int, P, c_ll, P],
         "qt_bcast_rows": [P, c_ll, c_int, c_int, c_int, P, c_int, c_ll, P],
+        "qt_sample_row_bytes": [], "qt_sample_args_bytes": [],
     }
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
-        f.restype = c_ll if name.endswith("_ws_bytes") else c_int
+        f.restype = c_ll if name.endswith(("_ws_bytes", "_row_bytes", "_args_bytes")) else c_int
     return L
 
 

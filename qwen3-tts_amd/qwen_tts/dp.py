@@ -98,6 +98,20 @@ def request_cost(input_ids, instruct_ids=None, frames=None, max_new_tokens=2048)
     return out
 
 
+def shard_row_params(gen: dict, mine: Sequence[int], n: int) -> dict:
+    """`gen` with every per-request sampling parameter (a list with one entry per request of the whole job:
+    GenParams.ROW_FIELDS) cut down to this rank's requests `mine`, in their order; scalars pass through."""
+    from .talker import GenParams
+    out = dict(gen)
+    for k in GenParams.ROW_FIELDS:
+        v = gen.get(k)
+        if isinstance(v, (list, tuple)):
+            if len(v) != n:
+                raise ValueError(f"{k} has {len(v)} entries for {n} requests")
+            out[k] = [v[i] for i in mine]
+    return out
+
+
 def dp_generate(model, input_ids, languages, speakers=None, instruct_ids=None, frames: Optional[Sequence[int]] = None,
                 slots: int = 8, group=None, gather: bool = True, decode: bool = False, **gen):
     """Serve a request list data-parallel over the ranks of `group` (or alone when torch.distributed is not
@@ -107,7 +121,8 @@ def dp_generate(model, input_ids, languages, speakers=None, instruct_ids=None, f
 
     model: a qwen_tts.model.TTSModel on this rank's GPU.  frames: optional per-request frame caps (known lengths /
     estimates); request i then stops after min(frames[i], max_new_tokens - 1) frames or at its EOS.  Each request
-    draws Philox stream i (its global index), so sampled results do not depend on the rank count.
+    draws Philox stream i (its global index), so sampled results do not depend on the rank count.  Sampling
+    parameters in **gen given as lists (one entry per request) are sharded by the same indices.
     Returns (codes list [F_i, 16], wavs list or None) on the group's rank 0 (every rank when gather=False returns its own
     share as {index: (codes, wav)}), None on other ranks."""
     world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -120,6 +135,7 @@ def dp_generate(model, input_ids, languages, speakers=None, instruct_ids=None, f
         sub = lambda xs: None if xs is None else [xs[i] for i in mine]  # noqa: E731
         if frames is not None:
             gen = dict(gen, frame_caps=sub(frames))
+        gen = shard_row_params(gen, mine, n)
         codes, _ = model.generate(input_ids=sub(input_ids), languages=sub(languages), speakers=sub(speakers),
                                   instruct_ids=sub(instruct_ids), max_batch=max(1, min(slots, len(mine))),
                                   philox_ids=mine, **gen)

@@ -162,8 +162,10 @@ class Qwen3TTSModel:
 
     def _merge_generate_kwargs(self, do_sample=None, top_k=None, top_p=None, temperature=None, repetition_penalty=None,
                                subtalker_dosample=None, subtalker_top_k=None, subtalker_top_p=None,
-                               subtalker_temperature=None, max_new_tokens=None, **kwargs) -> Dict[str, Any]:
-        """W:287-352: user value > generation_config.json > hard default."""
+                               subtalker_temperature=None, max_new_tokens=None, n_requests=None,
+                               **kwargs) -> Dict[str, Any]:
+        """W:287-352: user value > generation_config.json > hard default.  A user value may be a list with one entry
+        per request (TTSModel.generate; also `seed`): checked against n_requests, passed through as it is."""
         hard = dict(do_sample=True, top_k=50, top_p=1.0, temperature=0.9, repetition_penalty=1.05,
                     subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0, subtalker_temperature=0.9,
                     max_new_tokens=2048)
@@ -176,6 +178,14 @@ class Qwen3TTSModel:
             return hard[name]
 
         merged = dict(kwargs)
+        if n_requests is not None:
+            given = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature,
+                         repetition_penalty=repetition_penalty, subtalker_dosample=subtalker_dosample,
+                         subtalker_top_k=subtalker_top_k, subtalker_top_p=subtalker_top_p,
+                         subtalker_temperature=subtalker_temperature, seed=kwargs.get("seed"))
+            for name, v in given.items():
+                if isinstance(v, (list, tuple)) and len(v) != n_requests:
+                    raise ValueError(f"Batch size mismatch: text={n_requests}, {name}={len(v)}")
         merged.update(do_sample=pick("do_sample", do_sample), top_k=pick("top_k", top_k), top_p=pick("top_p", top_p),
                       temperature=pick("temperature", temperature),
                       repetition_penalty=pick("repetition_penalty", repetition_penalty),
@@ -248,7 +258,8 @@ class Qwen3TTSModel:
         input_ids, ref_ids, vcp, languages = self._voice_clone_inputs(text, language, ref_audio, ref_text,
                                                                       x_vector_only_mode, voice_clone_prompt)
         codes, _ = self.model.generate(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp, languages=languages,
-                                       non_streaming_mode=non_streaming_mode, **self._merge_generate_kwargs(**kwargs))
+                                       non_streaming_mode=non_streaming_mode,
+                                       **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
         refs = vcp.get("ref_code", None)
         dec = [torch.cat([refs[i].cpu().long(), c], 0) if refs is not None and refs[i] is not None else c
                for i, c in enumerate(codes)]
@@ -278,7 +289,7 @@ class Qwen3TTSModel:
         for i, pcm, last in self.model.stream(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp,
                                               languages=languages, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
-                                              **self._merge_generate_kwargs(**kwargs)):
+                                              **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, pcm.to(torch.float32).cpu().numpy(), sr, last
 
     def _voice_clone_inputs(self, text, language, ref_audio, ref_text, x_vector_only_mode, voice_clone_prompt):
@@ -340,7 +351,8 @@ class Qwen3TTSModel:
         input_ids = self._tokenize_texts([self._build_assistant_text(t) for t in texts])
         ins_ids = [None if not x else self._tokenize_texts([self._build_instruct_text(x)])[0] for x in instructs]
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
-                                       non_streaming_mode=non_streaming_mode, **self._merge_generate_kwargs(**kwargs))
+                                       non_streaming_mode=non_streaming_mode,
+                                       **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
         return self._decode(codes)
 
     # ---------------------------------------------------------------- custom voice (W:732-839)
@@ -376,7 +388,7 @@ class Qwen3TTSModel:
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        speakers=speakers, non_streaming_mode=non_streaming_mode,
-                                       **self._merge_generate_kwargs(**kwargs))
+                                       **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
         return self._decode(codes)
 
     @torch.no_grad()
@@ -395,7 +407,8 @@ class Qwen3TTSModel:
         for i, pcm, last in self.model.stream(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                               speakers=speakers, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
-                                              left_context=left_context, **self._merge_generate_kwargs(**kwargs)):
+                                              left_context=left_context,
+                                              **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, pcm.to(torch.float32).cpu().numpy(), sr, last
 
     def get_supported_speakers(self) -> Optional[List[str]]:

@@ -358,8 +358,10 @@ def sample(logits, R, V, ld, tok_out, *, seen=None, rep_penalty=1.0, n_generated
            suppress=(0, 0, -1), ignore_eos=False, finished=None, do_sample=False, top_k=0, top_p=1.0,
            temperature=1.0, seed=0, step=None, substep=0, codes=None, codes_ld=0, codes_w=16, codes_col=0,
            codes_step_off=0, row_base=0, emb=None, seed_ptr=None, debug_u=-1.0, emb16=None, emb2=None, algo=0,
-           ctr_stride=0, philox_row=None, force=None, pick=None, launch=True):
+           ctr_stride=0, philox_row=None, force=None, pick=None, rows=None, launch=True):
     """launch=False: return the qt_sample_args instead (for qt_cp_step_sampled).
+    rows: device table of R qt_sample_row records (sample_rows_table / a slice of one): row r takes do_sample, top_k,
+    top_p, temperature, rep_penalty and its Philox key from record r; those arguments and seed / seed_ptr are unused.
     step / n_generated: device int32 counters, one per row when ctr_stride = 1 (0: shared); philox_row: optional
     device int32 [R] Philox stream ids (default row_base + r).
     force / pick (teacher forcing, parity diagnostics): int32 buffers in the layout of `codes`; the choice is stored
@@ -380,6 +382,9 @@ def sample(logits, R, V, ld, tok_out, *, seen=None, rep_penalty=1.0, n_generated
     a.seed_ptr, a.debug_u, a.algo = ptr(seed_ptr), float(debug_u), int(algo)
     a.ctr_stride, a.philox_row = int(ctr_stride), ptr(philox_row)
     a.force, a.pick = ptr(force), ptr(pick)
+    if rows is not None:
+        assert rows.dtype == torch.uint8 and rows.is_contiguous() and rows.shape[0] >= R and rows.shape[1] == ROW_BYTES
+        a.rows = ptr(rows)
     if emb is not None:
         a.emb_table, a.emb_dim, a.emb_out, a.emb_ld = ptr(emb[0]), emb[0].shape[1], ptr(emb[1]), emb[2]
         if emb16 is not None:
@@ -389,6 +394,31 @@ def sample(logits, R, V, ld, tok_out, *, seen=None, rep_penalty=1.0, n_generated
     if not launch:
         return a
     check(_hip.lib().qt_sample(ctypes.byref(a), stream()), "qt_sample")
+
+
+ROW_BYTES = ctypes.sizeof(_hip.SampleRow)  # 32
+
+
+def sample_rows_table(n, device):
+    """Device table of n qt_sample_row records (uint8 [n][32]; cudaMalloc alignment covers the 16 bytes asked)."""
+    return torch.zeros(n, ROW_BYTES, dtype=torch.uint8, device=device)
+
+
+def pack_sample_rows(records):
+    """[(do_sample, top_k, top_p, temperature, rep_penalty, seed), ...] -> pinned uint8 [n][32] of qt_sample_row."""
+    arr = (_hip.SampleRow * len(records))()
+    for rec, (do_sample, top_k, top_p, temperature, rep_penalty, seed) in zip(arr, records):
+        rec.temperature, rec.top_p, rec.rep_penalty = float(temperature), float(top_p), float(rep_penalty)
+        rec.top_k, rec.do_sample, rec.seed = int(top_k or 0), int(bool(do_sample)), int(seed) & (2 ** 64 - 1)
+    host = torch.empty(len(records), ROW_BYTES, dtype=torch.uint8, pin_memory=True)
+    ctypes.memmove(host.data_ptr(), ctypes.addressof(arr), len(records) * ROW_BYTES)
+    return host
+
+
+def upload_sample_rows(table, b0, records):
+    """Write `records` (pack_sample_rows' tuples) into rows [b0, b0 + n) of a device table: one async copy on the
+    current stream, ordered before every sampler launched after it."""
+    table[b0:b0 + len(records)].copy_(pack_sample_rows(records), non_blocking=True)
 
 
 def rmsnorm(x, g, eps, out, M, N, rec=None, step=None, step_off=0, step_stride=0):

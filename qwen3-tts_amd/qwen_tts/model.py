@@ -297,12 +297,17 @@ class TTSModel:
         max_batch (not in the reference): with more requests than max_batch, decode them by continuous batching
         through max_batch batch rows (TalkerEngine.serve: a row is refilled with the next request as soon as its
         request ends).  Per request the result is that of the one-shot batched call (same Philox stream per request
-        index; per-row arithmetic does not depend on the batch's other rows)."""
+        index; per-row arithmetic does not depend on the batch's other rows).
+
+        Per-request sampling parameters (not in the reference): do_sample, top_k, top_p, temperature, the four
+        subtalker_* values, repetition_penalty and seed each take a list with one entry per request (GenParams);
+        request i then gets the codes of the same call made with its values as scalars."""
         emb, mask, trail, pad = self.build_prompts(input_ids, languages, speakers, instruct_ids, non_streaming_mode,
                                                    voice_clone_prompt, ref_ids)
         gp = GenParams(max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
                        subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
         B, P = emb.shape[0], emb.shape[1]
+        gp.check_rows(B)
         if (max_batch is not None and B > int(max_batch)) or frame_caps is not None:
             n_real = mask.sum(-1).tolist()
             reqs = [(emb[i, P - int(n_real[i]):], trail[i], None if frame_caps is None else frame_caps[i])
@@ -365,6 +370,7 @@ class TTSModel:
                                                        non_streaming_mode, voice_clone_prompt, ref_ids)
             gp = GenParams(max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
                            subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
+            gp.check_rows(emb.shape[0])
         except BaseException:
             # the side-stream reference decode holds a pooled codec slot: hand it back before the error propagates
             if started is not None:

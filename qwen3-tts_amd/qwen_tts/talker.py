@@ -360,13 +360,70 @@ class GenParams:
     # part of the session key: a new seed replays the same captured graph.
     seed: Optional[int] = None
 
+    # Per-request values: each of ROW_FIELDS may be a sequence with one entry per request of the call (in `seed`, a
+    # None entry means the call's seed).  The values then live in device tables read by the samplers (Session.rows_t /
+    # rows_c) instead of kernel arguments, so they are not part of the session key either: one session and one
+    # captured graph serve every mix.  eos_token_id, ignore_eos and max_new_tokens stay per call.
+    ROW_FIELDS = ("do_sample", "top_k", "top_p", "temperature", "subtalker_dosample", "subtalker_top_k",
+                  "subtalker_top_p", "subtalker_temperature", "repetition_penalty", "seed")
+
+    def __post_init__(self):
+        n = None
+        for f in self.ROW_FIELDS:
+            v = getattr(self, f)
+            if not isinstance(v, (list, tuple)):
+                continue
+            v = tuple(v)
+            setattr(self, f, v)
+            if n is not None and len(v) != n:
+                raise ValueError(f"per-request parameter lists differ in length: {f} has {len(v)}, others {n}")
+            n = len(v)
+            for x in v:
+                if x is None and f != "seed":
+                    raise ValueError(f"{f}: None is not a value (only `seed` takes None entries)")
+                if f.endswith("temperature") and not x > 0:
+                    raise ValueError(f"{f} entries must be > 0, got {x}")
+                if f.endswith("top_p") and not 0 < x <= 1:
+                    raise ValueError(f"{f} entries must be in (0, 1], got {x}")
+                if f.endswith("top_k") and x < 0:
+                    raise ValueError(f"{f} entries must be >= 0, got {x}")
+                if f == "repetition_penalty" and not x > 0:
+                    raise ValueError(f"{f} entries must be > 0, got {x}")
+        self.n_rows = n  # requests the lists speak for; None: every parameter is a scalar
+
+    @property
+    def per_row(self) -> bool:
+        return self.n_rows is not None
+
+    def check_rows(self, n: int):
+        """Raise unless the per-request lists (if any) have one entry for each of the call's n requests."""
+        if self.per_row and self.n_rows != n:
+            raise ValueError(f"per-request parameter lists have {self.n_rows} entries for {n} requests")
+
+    def at(self, f: str, i: int):
+        v = getattr(self, f)
+        return v[i] if isinstance(v, tuple) else v
+
+    def row_records(self, i: int, seed: int):
+        """Request i's sampler records (kernels.pack_sample_rows tuples): (talker, sub-talker).  seed: the call's
+        resolved seed, used where the request names none."""
+        sd = self.at("seed", i) if isinstance(self.seed, tuple) else None
+        sd = seed if sd is None else int(sd) & (2 ** 63 - 1)
+        return ((self.at("do_sample", i), self.at("top_k", i), self.at("top_p", i), self.at("temperature", i),
+                 self.at("repetition_penalty", i), sd),
+                (self.at("subtalker_dosample", i), self.at("subtalker_top_k", i), self.at("subtalker_top_p", i),
+                 self.at("subtalker_temperature", i), 1.0, sd))
+
     def key(self):
+        if self.per_row:  # what stays in kernel arguments
+            return ("per_row", self.eos_token_id, self.ignore_eos)
         return (self.do_sample, self.top_k, self.top_p, self.temperature, self.subtalker_dosample,
                 self.subtalker_top_k, self.subtalker_top_p, self.subtalker_temperature, self.eos_token_id,
                 self.repetition_penalty, self.ignore_eos)
 
     def resolve_seed(self) -> int:
-        if self.seed is not None:
+        """The call's seed (per-request lists: the seed of the requests whose entry is None)."""
+        if self.seed is not None and not isinstance(self.seed, tuple):
             return int(self.seed) & (2 ** 63 - 1)
         return int(torch.randint(0, 2 ** 63 - 1, (1,)).item())
 
@@ -424,6 +481,10 @@ class Session:
         self.pad_embed = f32(t.H)
         self.ws = K.new_workspace(dev)  # split-K scratch private to this session's stream
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)  # Philox key, read by the captured samplers
+        # per-request sampling parameters (gp.per_row): one record per batch row for the talker's sampler and one for
+        # the code predictor's (rep_penalty 1), uploaded by the prefills and read by every sampler of the row
+        self.rows_t = K.sample_rows_table(B, dev) if gp.per_row else None
+        self.rows_c = K.sample_rows_table(B, dev) if gp.per_row else None
         self.graph = None   # the frame graph of the current split factor (graphs[nsplit])
         self.graphs = {}    # talker attention split factor -> captured frame graph
         # prompt length P -> static prefill buffers (+ captured graph once P repeats); LRU, PREFILL_CACHE lengths
@@ -583,11 +644,15 @@ class TalkerEngine:
         eos = self._eos(gp)
         b1 = s.B if b1 is None else b1
         Hc = self.cp.H
+        if s.rows_t is not None:
+            how = {"rows": s.rows_t[b0:b1]}
+        else:
+            how = {"rep_penalty": gp.repetition_penalty, "do_sample": gp.do_sample, "top_k": gp.top_k,
+                   "top_p": gp.top_p, "temperature": gp.temperature, "seed_ptr": s.seed}
         K.sample(logits[b0:b1], b1 - b0, self.V, self.V, s.tok0[b0:b1], seen=s.seen[b0:b1],
-                 rep_penalty=gp.repetition_penalty, n_generated=s.n_gen[b0:b1], min_new_tokens=MIN_NEW_TOKENS, eos_id=eos,
+                 n_generated=s.n_gen[b0:b1], min_new_tokens=MIN_NEW_TOKENS, eos_id=eos,
                  suppress=(self.V - 1024, self.V, self.tc["codec_eos_token_id"]), ignore_eos=gp.ignore_eos,
-                 finished=s.finished[b0:b1], do_sample=gp.do_sample, top_k=gp.top_k, top_p=gp.top_p,
-                 temperature=gp.temperature, seed_ptr=s.seed, step=s.step[b0:b1], substep=substep,
+                 finished=s.finished[b0:b1], step=s.step[b0:b1], substep=substep, **how,
                  codes=s.codes[b0:b1], codes_ld=s.codes.shape[1] * self.G, codes_w=self.G, codes_col=0,
                  codes_step_off=codes_step_off, ctr_stride=1, philox_row=s.prow[b0:b1],
                  emb=(self.cp_in_tab0, s.cp_x.view(-1)[(2 * b0 + 1) * Hc:], 2 * Hc),
@@ -661,9 +726,13 @@ class TalkerEngine:
 
     def _cp_sample(self, s: Session, ln: CPLane, g, launch=True):
         c, gp = self.cp, s.gp
-        return K.sample(ln.logits, ln.nb, self.Vc, self.Vc, ln.tok, do_sample=gp.subtalker_dosample,
-                 top_k=gp.subtalker_top_k, top_p=gp.subtalker_top_p, temperature=gp.subtalker_temperature,
-                 seed_ptr=s.seed, step=s.step[ln.b0:ln.b1], substep=1 + g, codes=ln.codes,
+        if s.rows_c is not None:
+            how = {"rows": s.rows_c[ln.b0:ln.b1]}
+        else:
+            how = {"do_sample": gp.subtalker_dosample, "top_k": gp.subtalker_top_k, "top_p": gp.subtalker_top_p,
+                   "temperature": gp.subtalker_temperature, "seed_ptr": s.seed}
+        return K.sample(ln.logits, ln.nb, self.Vc, self.Vc, ln.tok, **how,
+                 step=s.step[ln.b0:ln.b1], substep=1 + g, codes=ln.codes,
                  codes_ld=s.codes.shape[1] * self.G, codes_w=self.G, codes_col=1 + g, codes_step_off=0, ctr_stride=1,
                  philox_row=s.prow[ln.b0:ln.b1],
                  emb=(self.cp_in_tabs[g], ln.x, c.H) if g < self.G - 2 else None,
@@ -696,6 +765,8 @@ class TalkerEngine:
         Returns (picks [B, F, 16] int64 cpu in the codes' layout, hidden [B, F, H] cpu), F = max F_b; entries past a
         row's F_b are unspecified."""
         import dataclasses
+        if gp.per_row:
+            raise ValueError("teacher_forced takes scalar sampling parameters")
         B, P, H = embeds.shape
         F = max(int(c.shape[0]) for c in ref_codes)
         gp = dataclasses.replace(gp, max_new_tokens=F + 1)
@@ -725,6 +796,7 @@ class TalkerEngine:
         caller's work, e.g. the first codec window); at that yield codes[:, 1, 0] is not written yet (EOS cannot occur
         there anyway: it is masked below min_new_tokens)."""
         B, P, H = embeds.shape
+        gp.check_rows(B)
         max_frames = max(gp.max_new_tokens - 1, 0)
         seed = gp.resolve_seed()
         main = torch.cuda.current_stream(self.dev)
@@ -733,7 +805,7 @@ class TalkerEngine:
             s = self.session(B, P, max(max_frames, 1), gp)
             sessions.append(s)
             with K.use_workspace(s.ws):
-                self._prefill(s, embeds, mask, trailing, tts_pad, seed, philox_ids)
+                self._prefill(s, embeds, mask, trailing, tts_pad, seed, philox_ids, gp=gp)
             yield from self._frames(sessions, [main], max_frames, use_graph, on_frames, every, first, grow, early_first)
         finally:
             self.release(sessions)
@@ -834,6 +906,7 @@ class TalkerEngine:
         philox_ids: optional Philox stream id per request (default its index i)."""
         n = len(requests)
         pids = list(range(n)) if philox_ids is None else [int(x) for x in philox_ids]
+        gp.check_rows(n)
         if n == 0:
             return
         B = max(1, min(slots, n))
@@ -858,7 +931,7 @@ class TalkerEngine:
                     emb[b, Pb - e.shape[0]:] = e
                     mask[b, Pb - e.shape[0]:] = 1
                     trail[b, :tr.shape[0]] = tr
-                self._prefill(s, emb, mask, trail, tts_pad, seed, pids[:B])
+                self._prefill(s, emb, mask, trail, tts_pad, seed, pids[:B], gp=gp)
                 s.hiddens[:, 0].copy_(s.past_hidden)
                 queue = list(range(B, n))
                 slot_req = list(range(B))
@@ -911,7 +984,8 @@ class TalkerEngine:
                         slot_req[b] = queue.pop(0) if queue else -1
                         if slot_req[b] >= 0:
                             slot_p[b] = int(requests[slot_req[b]][0].shape[0])
-                            self._prefill_slot(s, b, requests[slot_req[b]], pids[slot_req[b]])
+                            self._prefill_slot(s, b, requests[slot_req[b]], pids[slot_req[b]],
+                                               gp.row_records(slot_req[b], seed) if gp.per_row else None)
                         else:
                             s.finished[b:b + 1].fill_(1)  # idle slot: emits EOS until the session ends
                     while harvests and harvests[0][-1].query():
@@ -933,9 +1007,11 @@ class TalkerEngine:
         finally:
             self.release([s])
 
-    def _prefill_slot(self, s: Session, b: int, req, i: int):
+    def _prefill_slot(self, s: Session, b: int, req, i: int, records=None):
         """Start a request in batch row b (Philox stream id i): per-row state reset, single-request talker prefill into
-        row b's K/V (positions 0..P-1, no left padding), first token (M:1746-1800, 2044)."""
+        row b's K/V (positions 0..P-1, no left padding), first token (M:1746-1800, 2044).  records: the request's
+        (talker, sub-talker) sampler records of a per-row session, written to row b of its tables in stream order --
+        behind the frames already queued for the slot's previous request, before this one's first sample."""
         emb, trail = req[0], req[1]
         P, H = int(emb.shape[0]), self.talker.H
         t, dev = self.talker, self.dev
@@ -944,6 +1020,9 @@ class TalkerEngine:
         for z in (s.seen, s.finished, s.codes):
             z[b].zero_()
         s.prow[b:b + 1].fill_(i)
+        if s.rows_t is not None:
+            K.upload_sample_rows(s.rows_t, b, [records[0]])
+            K.upload_sample_rows(s.rows_c, b, [records[1]])
         s.meta["row_start"][b:b + 1].zero_()
         c = s.ctr.view(5, s.B)
         c[0, b:b + 1].zero_()
@@ -974,9 +1053,10 @@ class TalkerEngine:
         K.gemm(s.past_hidden[b:b + 1], self.codec_head, s.logits[b:b + 1], 1, H, self.V)
         self._sample_talker(s, s.logits, 0, 99, b, b + 1)
 
-    def _prefill(self, s: Session, embeds, mask, trailing, tts_pad, seed: int, philox_ids=None):
+    def _prefill(self, s: Session, embeds, mask, trailing, tts_pad, seed: int, philox_ids=None, gp=None):
         """Talker prefill of one row group (M:1746-1800 positions, M:2044 first token) into session s.
-        philox_ids: per-row Philox stream ids (default the row index)."""
+        philox_ids: per-row Philox stream ids (default the row index).  gp: the call's parameters -- a per-row
+        session's tables get the records of requests 0 .. B-1 before the first sample."""
         B, P, H = embeds.shape
         t = self.talker
         dev = self.dev
@@ -985,6 +1065,10 @@ class TalkerEngine:
         for z in (s.seen, s.finished, s.codes, s.ctr):
             z.zero_()
         s.seed.fill_(seed)
+        if s.rows_t is not None:
+            recs = [gp.row_records(i, seed) for i in range(B)]
+            K.upload_sample_rows(s.rows_t, 0, [r[0] for r in recs])
+            K.upload_sample_rows(s.rows_c, 0, [r[1] for r in recs])
         if philox_ids is None:
             torch.arange(B, dtype=torch.int32, device=dev, out=s.prow)
         else:
