@@ -20,14 +20,16 @@
 namespace {
 
 using qt_gemm_impl::GemmP;
+using qt_gemm_impl::GemmPlan;
+using qt_gemm_impl::GemmRoute;
+using qt_gemm_impl::GemmKnobs;
+using qt_gemm_impl::gemm_plan;
 
 // SnakeBeta exactly as qt_snake computes it (fp32 math on the stored activation)
 QT_DEV float snake1(float v, float al, float ib) {
   const float s = sinf(v * al);
   return v + ib * (s * s);
 }
-
-template <typename T> QT_DEV void load_vec(const T* p, float* o, int E);
 
 // Load the E-element A fragment of row m at padded k index kk (fp32 out), zero outside.
 template <typename AT, int E>
@@ -448,14 +450,14 @@ constexpr int IG_GPT = 3;  // staged 8-channel groups per thread (window rows <=
 #define IG_PD 1  // B-fragment prefetch distance in k tiles (2-4 measured slower: codec 41.0 / 34.1 / 38.2 vs 31.0 ms)
 #endif
 
-// G2 = 2 x 2 wave grid: wave (w >> 1, w & 1) owns BM/2 rows x NT/2 column tiles, so each B fragment is fetched by
-// 2 waves instead of 4 (the 4 x 1 layout is L1/TA-bound on the shared B fragments: 4 x NT KiB per k tile per block).
-template <typename AT, typename OT, int NT, int MI, bool G2>
+// 2 x 2 wave grid: wave (w >> 1, w & 1) owns BM/2 rows x NT/2 column tiles, so each B fragment is fetched by
+// 2 waves instead of 4 (a 4 x 1 layout is L1/TA-bound on the shared B fragments: 4 x NT KiB per k tile per block).
+template <typename AT, typename OT, int NT, int MI>
 __global__ __launch_bounds__(256) void igemm_k(GemmP p) {
   constexpr int BM = 64 * MI;  // output rows per block
-  constexpr int RT = G2 ? BM / 32 : MI;  // 16-row MFMA tiles per wave
-  constexpr int CT = G2 ? NT / 2 : NT;   // 16-column tiles per wave
-  static_assert(!G2 || NT % 2 == 0, "2 x 2 wave grid needs an even column tile count");
+  constexpr int RT = BM / 32;  // 16-row MFMA tiles per wave
+  constexpr int CT = NT / 2;   // 16-column tiles per wave
+  static_assert(NT % 2 == 0, "2 x 2 wave grid needs an even column tile count");
   extern __shared__ unsigned char ig_smem[];
   bf16_t* win = (bf16_t*)ig_smem;  // [2][WR][IG_LDSW]
   __shared__ float ss_row[BM];
@@ -468,8 +470,8 @@ __global__ __launch_bounds__(256) void igemm_k(GemmP p) {
   const int WR = BM + (taps - 1) * dil;
   const int tiles_t = (t_out + BM - 1) / BM;
   const int bi = blockIdx.x / tiles_t, t0 = (blockIdx.x - bi * tiles_t) * BM;
-  const int ntl = (p.N + 15) / 16, nt0 = blockIdx.y * NT + (G2 ? (w & 1) * CT : 0);
-  const int wrow = G2 ? (w >> 1) * (BM / 2) : w * (16 * MI);  // first output row of this wave in the tile
+  const int ntl = (p.N + 15) / 16, nt0 = blockIdx.y * NT + (w & 1) * CT;
+  const int wrow = (w >> 1) * (BM / 2);  // first output row of this wave in the tile
   const int nch = cin_pad / IG_KC, ktiles = p.Kp / IG_KC;
   const AT* A = (const AT*)p.A + (long long)bi * t_in * p.lda;
   const bool norm = p.rms != 0;
@@ -873,10 +875,11 @@ __global__ __launch_bounds__(256) void conv_n1_k(GemmP p) {
   }
 }
 
+// the decode GEMV instantiation of the plan: gemv_wt<WPB, U, NORM, NTL, F>
 template <typename WT, typename AT, typename OT, int WPB, int U, int F>
-void launch_gemv_f(const GemmP& p, int nt, hipStream_t s) {
-  const dim3 grid(nt, p.ks, (p.M + p.mr - 1) / p.mr), block(WPB * 64);
-  if (p.ntl) {
+void launch_gemv_f(const GemmP& p, const GemmPlan& pl, hipStream_t s) {
+  const dim3 grid((p.N + 15) / 16, p.ks, (p.M + p.mr - 1) / p.mr), block(WPB * 64);
+  if (pl.nt_loads) {
     if (p.rms) hipLaunchKernelGGL((gemv_wt<WT, AT, OT, WPB, U, true, true, F>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((gemv_wt<WT, AT, OT, WPB, U, false, true, F>), grid, block, 0, s, p);
   } else {
@@ -884,169 +887,84 @@ void launch_gemv_f(const GemmP& p, int nt, hipStream_t s) {
     else hipLaunchKernelGGL((gemv_wt<WT, AT, OT, WPB, U, false, false, F>), grid, block, 0, s, p);
   }
 }
-
-// fold factor from the rows per block (bf16 weights): 4 for <= 4 rows, 2 for <= 8 (QT_GEMV_FOLD=1 disables)
 template <typename WT, typename AT, typename OT, int WPB, int U>
-void launch_gemv_u(const GemmP& p, int nt, hipStream_t s) {
-  static const int fold_env = qt_knob("QT_GEMV_FOLD", 4);
-  if constexpr (sizeof(WT) == 2) {
-    if (fold_env >= 4 && p.mr <= 4) return launch_gemv_f<WT, AT, OT, WPB, U, 4>(p, nt, s);
-    if (fold_env >= 2 && p.mr <= 8) return launch_gemv_f<WT, AT, OT, WPB, U, 2>(p, nt, s);
+void launch_gemv_u(const GemmP& p, const GemmPlan& pl, hipStream_t s) {
+  if constexpr (sizeof(WT) == 2) {  // the row folds exist for bf16 weights
+    if (pl.fold == 4) return launch_gemv_f<WT, AT, OT, WPB, U, 4>(p, pl, s);
+    if (pl.fold == 2) return launch_gemv_f<WT, AT, OT, WPB, U, 2>(p, pl, s);
   }
-  launch_gemv_f<WT, AT, OT, WPB, U, 1>(p, nt, s);
+  launch_gemv_f<WT, AT, OT, WPB, U, 1>(p, pl, s);
 }
-
-// U = k tiles in flight per wave: 8 when a wave owns 5..8 (one round trip instead of two).  Forcing U = 8 on
-// every shape, or 16, was measured slower (register pressure; profiles/r01_gemv_variants_ab.jsonl).
-// QT_GEMV_U (4 / 8) overrides for A/B measurement.
 template <typename WT, typename AT, typename OT, int WPB>
-void launch_gemv(const GemmP& p, int nt, int per, hipStream_t s) {
-  static const int u_env = qt_knob("QT_GEMV_U", 0);
-  const int u = u_env ? u_env : ((per > 4 && per <= 8) ? 8 : 4);
-  if (u >= 8) launch_gemv_u<WT, AT, OT, WPB, 8>(p, nt, s);
-  else launch_gemv_u<WT, AT, OT, WPB, 4>(p, nt, s);
+void launch_gemv(const GemmP& p, const GemmPlan& pl, hipStream_t s) {
+  if (pl.u == 8) launch_gemv_u<WT, AT, OT, WPB, 8>(p, pl, s);
+  else launch_gemv_u<WT, AT, OT, WPB, 4>(p, pl, s);
 }
 
-// largest row count run as the decode GEMV over row groups of gemv_mr() rows (QT_GEMV_MAX_M / QT_GEMV_MR override,
-// measurement; 16 = decode only)
-inline int gemv_max_m() {
-  static const int v = qt_knob("QT_GEMV_MAX_M", 256);
-  return v;
-}
-inline int gemv_mr() {
-  static const int v = qt_knob("QT_GEMV_MR", 16);
-  return std::max(1, std::min(16, v));
-}
-
-// largest row count served by the skinny GEMM gemm_sk_k (QT_SK=0 disables it: measurement)
-inline int sk_max_m() {
-  static const int v = [] {
-    if (qt_knob("QT_SK", 1) == 0) return 0;
-    return std::min(qt_knob("QT_SK_MAX_M", 48), 64);  // (48 vs 64: bench --workload vd64 451 vs 442 audio-s/s)
-  }();
-  return v;
-}
-
-// largest row count of a conv routed to im2col + the linear GEMMs (QT_IM2COL_MAX_M, measurement)
-inline int im2col_max_m() {
-  // (first streamed window at B = 8: 256 rows 1.70 ms, 512 1.39, 1024 1.39, 2048 1.40; profiles/r03_codec_first_window_im2col.txt)
-  static const int v = qt_knob("QT_IM2COL_MAX_M", 1024);
-  return v;
-}
-
-// smallest row count routed to the LDS-tiled implicit GEMM (QT_IGEMM_MIN_M overrides, measurement)
-inline int igemm_min_m() {
-  static const int v = qt_knob("QT_IGEMM_MIN_M", 128);
-  return v;
-}
-
-// the LDS-staged prefill GEMM (gemm_pf_k) for taps == 0 linears; QT_PF=0 keeps them on igemm_k (measurement)
-inline bool pf_on() {
-  static const bool v = (qt_knob("QT_PF", 1) != 0);
-  return v;
-}
-// fewest rows served by gemm_pf_k (QT_PF_MIN_M, measurement; default the igemm_k threshold)
-inline int pf_min_m() {
-  static const int v = qt_knob("QT_PF_MIN_M", 0);
-  return v;
-}
-// widest output served by gemm_pf_k (QT_PF_NMAX, measurement; 0 = any)
-inline int pf_nmax() {
-  static const int v = qt_knob("QT_PF_NMAX", 0);
-  return v;
-}
-
-// gemm_pf_k serves bf16-A linears (the bf16 residual shadow, attention / SwiGLU outputs); with fp32 A its 32 KiB
-// per-stage A fetch from beyond L2 is not hidden by one stage of prefetch (M=680 gate-up 184 vs 107 us on igemm_k)
-template <typename WT, typename AT>
-bool pf_route(const GemmP& p) {
-  return sizeof(WT) == 2 && sizeof(AT) == 2 && p.taps == 0 && pf_on() && p.a_index == nullptr && p.gamma == nullptr &&
-         p.N >= 32 && (pf_nmax() == 0 || p.N <= pf_nmax()) && (p.pf_small || p.M >= std::max(igemm_min_m(), pf_min_m())) && p.mr > 16 && p.Klog % 8 == 0 && p.lda % 8 == 0 && !p.a_elu &&
-         p.sn_a == nullptr && !p.no_igemm;
-}
-
-// gemm_pf2_k (deep-pipelined LDS-DMA prefill GEMM, gemm_pf2.hip): QT_PF2=0 keeps gemm_pf_k (A/B)
-inline int pf2_mode() {
-  static const int v = qt_knob("QT_PF2", 1);
-  return v;
-}
-
-
-template <typename WT, typename AT, typename OT>
-int launch(const GemmP& p, hipStream_t s) {
+template <typename AT, typename OT>
+void launch_igemm(const GemmP& p, const GemmPlan& pl, hipStream_t s) {
   const int nt = (p.N + 15) / 16;
-  constexpr int KT = sizeof(WT) == 2 ? 32 : 16;
-  if constexpr (sizeof(WT) == 2 && sizeof(AT) == 2) {
-    if (p.sk) {
-      if constexpr (std::is_same<OT, float>::value) qt_gemm_impl::launch_sk_f32(p, s);
-      else qt_gemm_impl::launch_sk_bf16(p, s);
-      return hipGetLastError() == hipSuccess ? 0 : QT_ERR_LAUNCH;
-    }
+  const int taps = p.taps == 0 ? 1 : p.taps, dil = p.taps == 0 ? 1 : p.dil;
+  const int t_out = p.taps == 0 ? p.M : p.t_out, batches = p.taps == 0 ? 1 : p.M / p.t_out;
+  const int bm = 64 * pl.mi;
+  const int WR = bm + (taps - 1) * dil;
+  const size_t smem = (size_t)2 * WR * IG_LDSW * sizeof(bf16_t);
+  const dim3 grid(batches * ((t_out + bm - 1) / bm), (nt + pl.ntb - 1) / pl.ntb);
+#define IG_GO(N_, M_) hipLaunchKernelGGL((igemm_k<AT, OT, N_, M_>), grid, dim3(256), smem, s, p)
+  switch (pl.ntb * 10 + pl.mi) {
+    case 62: IG_GO(6, 2); break;
+    case 61: IG_GO(6, 1); break;
+    case 42: IG_GO(4, 2); break;
+    case 41: IG_GO(4, 1); break;
+    case 81: IG_GO(8, 1); break;
+    default: IG_GO(8, 2); break;
   }
-  if (p.mr <= 16 && p.taps == 0 && p.Klog % KT == 0 && p.gamma == nullptr && !p.a_elu) {
-    const int kts = (p.Kp / KT + p.ks - 1) / p.ks;  // k tiles per split
-    if (kts >= 48 && p.wpb_max >= 16) launch_gemv<WT, AT, OT, 16>(p, nt, (kts + 15) / 16, s);
-    else if (kts >= 16 && p.wpb_max >= 8) launch_gemv<WT, AT, OT, 8>(p, nt, (kts + 7) / 8, s);
-    else launch_gemv<WT, AT, OT, 4>(p, nt, (kts + 3) / 4, s);
-  } else if (p.N == 1 && p.taps > 0 && p.taps * p.cin_pad <= 2048 && p.act == QT_ACT_NONE &&
-             p.epi != QT_EPI_SWIGLU && !p.rms &&
-             p.colscale == nullptr && p.a_index == nullptr && p.gamma == nullptr &&
-             (size_t)(256 + (p.taps - 1) * p.dil) * 33 * sizeof(float) <= 64 * 1024) {
-    const size_t smem = (size_t)(256 + (p.taps - 1) * p.dil) * 33 * sizeof(float);
-    const int batches = p.M / p.t_out;
-    hipLaunchKernelGGL((conv_n1_k<AT, WT, OT>), dim3(batches * ((p.t_out + 255) / 256)), dim3(256), smem, s, p);
-  } else if (p.M <= 16) {
-    hipLaunchKernelGGL((gemm_wt<WT, AT, OT, 1, 8>), dim3(nt, 1), dim3(512), 0, s, p);
-  } else if (pf_route<WT, AT>(p) && pf2_mode() && p.Klog % 64 == 0 && p.Kp == p.Klog &&
-             ((size_t)p.A & 15) == 0) {
-    if constexpr (std::is_same<OT, float>::value) qt_gemm_impl::launch_pf2_auto_f32(p, s);
-    else qt_gemm_impl::launch_pf2_auto_bf16(p, s);
-  } else if (pf_route<WT, AT>(p)) {
-    // prefill linears: LDS-staged A and B, 128 x 128 tiles (128 x 64 when that leaves < 256 blocks)
-    const int mt = (p.M + PF_BM - 1) / PF_BM;
-    const bool narrow = (long long)mt * ((nt + 7) / 8) < 256;
-    if (narrow) hipLaunchKernelGGL((gemm_pf_k<AT, OT, 4>), dim3(mt, (nt + 3) / 4), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((gemm_pf_k<AT, OT, 8>), dim3(mt, (nt + 7) / 8), dim3(256), 0, s, p);
-  } else if (sizeof(WT) == 2 && p.a_index == nullptr && p.gamma == nullptr && p.N >= 32 &&
-             p.M >= (p.taps > 0 ? 16 : igemm_min_m()) &&
-             (p.taps == 0 ? p.Klog % 8 == 0 : IG_BM + (p.taps - 1) * p.dil <= 256 * IG_GPT / 4) && !p.no_igemm) {
-    const int taps = p.taps == 0 ? 1 : p.taps, dil = p.taps == 0 ? 1 : p.dil;
-    const int t_out = p.taps == 0 ? p.M : p.t_out, batches = p.taps == 0 ? 1 : p.M / p.t_out;
-    // column tile per block: 6 x 16 for 96 / 192-channel layers (no idle tiles, the snake-staged window is
-    // shared by all of a row tile's columns), else 8 x 16; QT_IGEMM_CFG = "NT,MI" overrides (measurement)
-    static const int cfg = [] { const char* e = qt_knob_str("QT_IGEMM_CFG"); return e ? atoi(e) * 10 + atoi(e + 2) : 0; }();
-    // QT_IGEMM_G2 = 0 selects the 4 x 1 wave layout (measurement); default 2 x 2
-    static const int g2 = qt_knob("QT_IGEMM_G2", 1);
-    int ntb = (nt % 6 == 0 && nt <= 12) ? 6 : 8, mi = 2;
-    // short windows (a streamed codec window, 1-3 frames x batch rows per conv): 64-row tiles and 4 (6) column
-    // tiles per block when the default tiling leaves fewer than 256 blocks -- the first streamed window's feed
-    // 2.53 -> 2.08 ms at B=8 (tools/codec_feed_prof.py)
-    if (!cfg) {
-      const int tout = p.taps == 0 ? p.M : p.t_out, nb = p.taps == 0 ? 1 : p.M / p.t_out;
-      const long long blocks = (long long)nb * ((tout + 127) / 128) * ((nt + ntb - 1) / ntb);
-      if (blocks < 256) { mi = 1; ntb = ntb == 6 ? 6 : 4; }
-    }
-    if (cfg) { ntb = cfg / 10; mi = cfg % 10; }
-    const int bm = 64 * mi;
-    const int WR = bm + (taps - 1) * dil;
-    const size_t smem = (size_t)2 * WR * IG_LDSW * sizeof(bf16_t);
-    dim3 grid(batches * ((t_out + bm - 1) / bm), (nt + ntb - 1) / ntb);
-#define IG_GO(N_, M_)                                                                            \
-  do {                                                                                           \
-    if (g2) hipLaunchKernelGGL((igemm_k<AT, OT, N_, M_, true>), grid, dim3(256), smem, s, p);    \
-    else hipLaunchKernelGGL((igemm_k<AT, OT, N_, M_, false>), grid, dim3(256), smem, s, p);      \
-  } while (0)
-    if (ntb == 6 && mi == 2) IG_GO(6, 2);
-    else if (ntb == 6 && mi == 1) IG_GO(6, 1);
-    else if (ntb == 4 && mi == 2) IG_GO(4, 2);
-    else if (ntb == 4 && mi == 1) IG_GO(4, 1);
-    else if (ntb == 8 && mi == 1) IG_GO(8, 1);
-    else IG_GO(8, 2);
 #undef IG_GO
-  } else if (p.M <= 32) {
-    hipLaunchKernelGGL((gemm_wt<WT, AT, OT, 2, 8>), dim3(nt, (p.M + 31) / 32), dim3(512), 0, s, p);
-  } else {
-    hipLaunchKernelGGL((gemm_wt<WT, AT, OT, 4, 4>), dim3(nt, (p.M + 63) / 64), dim3(256), 0, s, p);
+}
+
+// launch the kernel family the plan names (gemm_route.h decides; nothing is decided here)
+template <typename WT, typename AT, typename OT>
+int launch(const GemmP& p, const GemmPlan& pl, GemmRoute route, hipStream_t s) {
+  const int nt = (p.N + 15) / 16;
+  constexpr bool BF2 = sizeof(WT) == 2 && sizeof(AT) == 2;  // SK / PF2 / PF: bf16 A and bf16 weights (the planner's rule)
+  switch (route) {
+    case GemmRoute::SK:
+      if constexpr (!BF2) return QT_ERR_DTYPE;
+      else if constexpr (std::is_same<OT, float>::value) qt_gemm_impl::launch_sk_f32(p, pl.sk_mi, s);
+      else qt_gemm_impl::launch_sk_bf16(p, pl.sk_mi, s);
+      break;
+    case GemmRoute::GEMV:
+      if (pl.wpb == 16) launch_gemv<WT, AT, OT, 16>(p, pl, s);
+      else if (pl.wpb == 8) launch_gemv<WT, AT, OT, 8>(p, pl, s);
+      else launch_gemv<WT, AT, OT, 4>(p, pl, s);
+      break;
+    case GemmRoute::CONV_N1: {
+      const size_t smem = (size_t)(256 + (p.taps - 1) * p.dil) * 33 * sizeof(float);
+      const int batches = p.M / p.t_out;
+      hipLaunchKernelGGL((conv_n1_k<AT, WT, OT>), dim3(batches * ((p.t_out + 255) / 256)), dim3(256), smem, s, p);
+      break;
+    }
+    case GemmRoute::WT_1x8: hipLaunchKernelGGL((gemm_wt<WT, AT, OT, 1, 8>), dim3(nt, 1), dim3(512), 0, s, p); break;
+    case GemmRoute::PF2:
+      if constexpr (!BF2) return QT_ERR_DTYPE;
+      else if constexpr (std::is_same<OT, float>::value) qt_gemm_impl::launch_pf2_f32(p, pl.pf2_cfg, pl.pf2_ks, s);
+      else qt_gemm_impl::launch_pf2_bf16(p, pl.pf2_cfg, pl.pf2_ks, s);
+      break;
+    case GemmRoute::PF: {
+      const int mt = (p.M + PF_BM - 1) / PF_BM;
+      if constexpr (!BF2) return QT_ERR_DTYPE;
+      else if (pl.ntb == 4) hipLaunchKernelGGL((gemm_pf_k<AT, OT, 4>), dim3(mt, (nt + 3) / 4), dim3(256), 0, s, p);
+      else hipLaunchKernelGGL((gemm_pf_k<AT, OT, 8>), dim3(mt, (nt + 7) / 8), dim3(256), 0, s, p);
+      break;
+    }
+    case GemmRoute::IGEMM: launch_igemm<AT, OT>(p, pl, s); break;
+    case GemmRoute::WT_2x8:
+      hipLaunchKernelGGL((gemm_wt<WT, AT, OT, 2, 8>), dim3(nt, (p.M + 31) / 32), dim3(512), 0, s, p);
+      break;
+    case GemmRoute::WT_4x4:
+      hipLaunchKernelGGL((gemm_wt<WT, AT, OT, 4, 4>), dim3(nt, (p.M + 63) / 64), dim3(256), 0, s, p);
+      break;
+    default: return QT_ERR_ARG;  // NONE / IM2COL are resolved by qt_gemm
   }
   return hipGetLastError() == hipSuccess ? 0 : QT_ERR_LAUNCH;
 }
@@ -1098,179 +1016,82 @@ __global__ __launch_bounds__(256) void im2col_k(GemmP p, bf16_t* __restrict__ ou
       u32x4_t{pack2bf(v[0], v[1]), pack2bf(v[2], v[3]), pack2bf(v[4], v[5]), pack2bf(v[6], v[7])};
 }
 
-// short conv windows (<= 1024 rows: a streamed codec window's stages; tens of rows, K = taps x cin_pad up to ~7k): igemm_k's
-// 128-row tiles leave a few dozen blocks each walking hundreds of k chunks (~110-130 us per conv at B = 8 x 1 frame);
-// as im2col + the linear routes (decode GEMV / skinny GEMMs / split-K prefill GEMM) the weights stream over the chip.
-// The im2col image lives in the upper half of the caller's workspace.  QT_IM2COL=0 disables (measurement).
-constexpr long long IM2COL_WS = 16ll << 20, IM2COL_OFF = 8ll << 20;
-inline bool im2col_route(const qt_gemm_args* a) {
-  static const int env = qt_knob("QT_IM2COL", 1);
-  if (!env || a->taps <= 0 || a->w_dtype != QT_BF16 || a->M <= 0 || a->M > im2col_max_m() || a->rmsnorm ||
-      a->gamma != nullptr || a->a_index != nullptr || !a->ws || a->ws_bytes < IM2COL_WS || a->t_out <= 0 ||
-      a->cin_pad % 32 || a->cin % 8 || a->splitk == 1)
-    return false;
-  const long long kp = (long long)a->taps * a->cin_pad;
-  return (long long)a->M * kp * 2 <= IM2COL_WS - IM2COL_OFF && a->M % a->t_out == 0;
+// the routing constants: compiled-in defaults, read from the environment once by a probe build (tools/*.sh A/B runs)
+const GemmKnobs& gemm_knobs() {
+  static const GemmKnobs knobs = [] {
+    GemmKnobs k;
+    if (kProbe) {
+#define QT_K(f, name) k.f = qt_knob(name, k.f)
+      QT_K(gemv_fold, "QT_GEMV_FOLD"); QT_K(gemv_u, "QT_GEMV_U"); QT_K(gemv_max_m, "QT_GEMV_MAX_M");
+      QT_K(gemv_nt, "QT_GEMV_NT"); QT_K(gemv_wpb, "QT_GEMV_WPB"); QT_K(gemv_split_auto, "QT_GEMV_SPLIT_AUTO");
+      QT_K(gemv_rg, "QT_GEMV_RG"); QT_K(skinny, "QT_SKINNY"); QT_K(sk, "QT_SK"); QT_K(sk_max_m, "QT_SK_MAX_M");
+      QT_K(im2col, "QT_IM2COL"); QT_K(im2col_max_m, "QT_IM2COL_MAX_M"); QT_K(igemm_min_m, "QT_IGEMM_MIN_M");
+      QT_K(no_igemm, "QT_NO_IGEMM"); QT_K(pf, "QT_PF"); QT_K(pf2_split, "QT_PF2_SPLIT"); QT_K(pf2_cfg, "QT_PF2_CFG");
+      QT_K(pf2_pp, "QT_PF2_PP");
+#undef QT_K
+      const char* e = qt_knob_str("QT_IGEMM_CFG");  // "NT,MI"
+      k.igemm_cfg = e ? atoi(e) * 10 + atoi(e + 2) : 0;
+    }
+    return k;
+  }();
+  return knobs;
+}
+
+// the kernels' argument block of one call
+GemmP gemm_params(const qt_gemm_args& a, const GemmPlan& pl) {
+  GemmP p;
+  p.M = a.M; p.N = a.N; p.Kp = pl.kp; p.Klog = a.K;
+  p.A = a.A; p.lda = a.lda; p.a_index = a.a_index; p.W = a.W;
+  p.gamma = a.gamma; p.eps = a.eps; p.rms = a.rmsnorm || a.gamma != nullptr; p.bias = a.bias; p.colscale = a.colscale;
+  p.act = a.act; p.epi = a.epi; p.out = a.out; p.ldo = a.ldo;
+  p.taps = a.taps > 0 ? a.taps : 0; p.dil = a.dil > 0 ? a.dil : 1; p.cin = a.cin; p.cin_pad = a.cin_pad;
+  p.t_in = a.t_in; p.t_out = a.t_out; p.t_off = a.t_off;
+  p.ks = pl.ks; p.mr = std::max(1, pl.mr);
+  p.cnt = pl.ws_split ? (unsigned*)a.ws : nullptr;
+  p.part = pl.ws_split ? (float*)((char*)a.ws + qt_gemm_impl::WS_CNT_BYTES) : nullptr;
+  p.sn_a = a.snake_alpha; p.sn_ib = a.snake_inv_beta;
+  p.a_elu = a.a_act == QT_AACT_ELU;
+  p.out2 = (bf16_t*)a.out2; p.ldo2 = a.ldo2;
+  return p;
 }
 }  // namespace
 
+extern "C" int qt_gemm_route(const qt_gemm_args* a, qt_gemm_route_info* info) {
+  if (!a || !info) return QT_ERR_ARG;
+  const GemmPlan pl = gemm_plan(*a, gemm_knobs());
+  *info = qt_gemm_route_info{};
+  if (pl.route == GemmRoute::NONE) return pl.err;
+  *info = qt_gemm_route_info{(int)pl.route, (int)pl.inner, pl.ks, pl.mr, pl.wpb, pl.u, pl.fold, pl.nt_loads,
+                             pl.pf2_cfg, pl.pf2_ks, pl.ntb, pl.mi, pl.sk_mi, pl.ws_split ? 1 : 0};
+  return 0;
+}
+
 extern "C" int qt_gemm(const qt_gemm_args* a, void* stream) {
-  if (!a || !a->A || !a->W || !a->out) return QT_ERR_ARG;
-  if (im2col_route(a)) {
-    GemmP q;
-    q.M = a->M; q.A = a->A; q.lda = a->lda; q.taps = a->taps; q.dil = a->dil > 0 ? a->dil : 1; q.cin = a->cin;
-    q.cin_pad = a->cin_pad; q.t_in = a->t_in; q.t_out = a->t_out; q.t_off = a->t_off; q.Kp = a->taps * a->cin_pad;
-    q.a_elu = a->a_act == QT_AACT_ELU; q.sn_a = a->snake_alpha; q.sn_ib = a->snake_inv_beta;
-    bf16_t* img = (bf16_t*)((char*)a->ws + IM2COL_OFF);
-    const long long n = (long long)a->M * a->taps * (a->cin_pad / 8);
-    hipStream_t s = (hipStream_t)stream;
-    if (a->a_dtype == QT_BF16) hipLaunchKernelGGL(im2col_k<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, img);
-    else if (a->a_dtype == QT_F32) hipLaunchKernelGGL(im2col_k<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, q, img);
-    else return QT_ERR_DTYPE;
-    if (hipGetLastError() != hipSuccess) return QT_ERR_LAUNCH;
-    qt_gemm_args b = *a;
-    b.taps = 0; b.A = img; b.a_dtype = QT_BF16; b.lda = q.Kp; b.K = (int)q.Kp; b.a_act = QT_AACT_NONE;
-    b.snake_alpha = nullptr; b.snake_inv_beta = nullptr; b.ws_bytes = IM2COL_OFF;  // split records below the image
-    return qt_gemm(&b, stream);
-  }
-  const int E = a->w_dtype == QT_BF16 ? 8 : 4;
-  const int KT = 4 * E;
-  GemmP p;
-  p.M = a->M; p.N = a->N;
-  p.taps = a->taps; p.dil = a->dil > 0 ? a->dil : 1; p.cin = a->cin; p.cin_pad = a->cin_pad;
-  p.t_in = a->t_in; p.t_out = a->t_out; p.t_off = a->t_off;
-  if (a->taps > 0) {
-    if (a->cin_pad % KT || a->cin % E || a->t_out <= 0) return QT_ERR_SHAPE;
-    p.Kp = a->taps * a->cin_pad;
-  } else {
-    p.Kp = (a->K + KT - 1) / KT * KT;
-    if (a->K % E) return QT_ERR_SHAPE;
-  }
-  p.Klog = a->K;
-  if (a->M <= 0 || a->N <= 0 || (a->epi == QT_EPI_SWIGLU && a->N % 16)) return QT_ERR_SHAPE;
-  if (a->epi == QT_EPI_SWIGLU && (a->bias || a->colscale)) return QT_ERR_ARG;
-  p.A = a->A; p.lda = a->lda; p.a_index = a->a_index; p.W = a->W;
-  p.gamma = a->gamma; p.eps = a->eps; p.rms = a->rmsnorm || a->gamma != nullptr; p.bias = a->bias; p.colscale = a->colscale;
-  p.act = a->act; p.epi = a->epi; p.out = a->out; p.ldo = a->ldo;
-  p.out2 = (bf16_t*)a->out2; p.ldo2 = a->ldo2;
-  if (p.out2 && (a->taps > 0 || a->epi == QT_EPI_SWIGLU || a->o_dtype != QT_F32)) return QT_ERR_ARG;
-  p.sn_a = a->snake_alpha; p.sn_ib = a->snake_inv_beta;
-  if ((p.sn_a == nullptr) != (p.sn_ib == nullptr)) return QT_ERR_ARG;
-  if (a->a_act != QT_AACT_NONE && a->a_act != QT_AACT_ELU) return QT_ERR_ARG;
-  if (a->act < QT_ACT_NONE || a->act > QT_ACT_RELU_TANH) return QT_ERR_ARG;
-  p.a_elu = a->a_act == QT_AACT_ELU;
-  static const int no_ig = qt_knob("QT_NO_IGEMM", 0);
-  p.no_igemm = no_ig;
-  // weights streamed once per frame (talker-size matrices) bypass cache retention so the re-read code-predictor
-  // weights stay in L2 / Infinity Cache; QT_GEMV_NT=0/1 forces it off/on for every decode GEMV (measurement)
-  static const int nt_env = qt_knob("QT_GEMV_NT", -1);
-  const long long wbytes = (long long)((a->N + 15) / 16) * 16 * p.Kp * (a->w_dtype == QT_BF16 ? 2 : 4);
-  p.ntl = nt_env >= 0 ? nt_env : (wbytes >= (16ll << 20));
-  // split-K for the decode GEMV when it has too few column tiles to fill 256 CUs twice
-  p.ks = 1; p.cnt = nullptr; p.part = nullptr; p.part_bytes = 0;
-  if (a->M > 16 && a->ws && a->ws_bytes >= QT_GEMM_WS_MIN && a->splitk != 1) {
-    // gemm_pf2_k split-K records (narrow outputs with few tiles, gemm_pf2.hip pf2_splits)
-    p.cnt = (unsigned*)a->ws;
-    p.part = (float*)((char*)a->ws + 4096 * sizeof(unsigned));
-    p.part_bytes = a->ws_bytes - 4096 * (long long)sizeof(unsigned);
-  }
-  // wide grids use smaller blocks so several fit per CU (fewer block rounds; measured: N=12288 K=2048
-  // 14.7 us at 16 waves/block -> 12.0 at 4); QT_GEMV_WPB overrides the cap for A/B measurement
-  static const int wpb_env = qt_knob("QT_GEMV_WPB", 0);
-  const int ntc = (a->N + 15) / 16;
-  p.wpb_max = wpb_env > 0 ? wpb_env : (ntc > 512 ? 4 : (ntc > 256 ? 8 : 16));
-  const int ntl = (a->N + 15) / 16, ktl = p.Kp / KT;
-  if (a->M <= 16 && a->taps == 0 && a->K % KT == 0 && a->gamma == nullptr && a->ws && a->ws_bytes >= QT_GEMM_WS_MIN &&
-      a->splitk != 1 && ntl <= 4096) {
-    // auto: split only deep-K shapes on < 256 column tiles (the arrival / partial round trips pay only when they
-    // remove weight round trips).  Measured cold, paired-A GEMV, partial loads of four splits in flight:
-    // 2048x6144 11.4 (no split) / 10.9 (2) / 10.3 us (4), 1024x3072 8.5 / 7.6 / 7.1 us; other shapes lose.
-    // In the frame graph split 2 wins (bench 158.6 vs 157.2 audio-s/s, same box): QT_GEMV_SPLIT_AUTO overrides
-    const int wpb1 = ktl >= 48 ? 16 : (ktl >= 16 ? 8 : 4), per1 = (ktl + wpb1 - 1) / wpb1;
-    static const int ks_auto = qt_knob("QT_GEMV_SPLIT_AUTO", 2);
-    int ks = a->splitk > 1 ? a->splitk : ((per1 > 4 && ntl < 256) ? ks_auto : 1);
-    ks = std::max(1, std::min({ks, 16, ktl / 2}));
-    const size_t need = 4096 * sizeof(unsigned) + (size_t)ntl * ks * (64 * 4 + 16) * sizeof(float);
-    if (ks > 1 && need <= (size_t)a->ws_bytes) {
-      p.ks = ks;
-      p.cnt = (unsigned*)a->ws;
-      p.part = (float*)((char*)a->ws + 4096 * sizeof(unsigned));
-    }
-  }
-  // decode GEMV row groups (bf16 weights): rows split over gridDim.z blocks instead of K over gridDim.y for
-  // shapes with <= 128 column tiles (measured cold, M = 8, two groups of 4 rows with fold 4: talker o 6.0 -> 5.3,
-  // talker down 10.9 (split-K 2) -> 9.4, CP down 7.6 -> 6.5, CP lm_head 4.9 -> 4.5 us; wider shapes lose:
-  // talker qkv 6.7 -> 9.6).  QT_GEMV_RG = n forces n groups, 1 = off, 0 = auto.
-  p.mr = std::max(1, a->M);
-  // 17..256 rows of bf16 A x bf16 weights (prefills of streaming-text / voice-clone prompts, single-request refills):
-  // three kernels, picked by the per-launch times of tools/prefill_gemm_bench.py at 1.7B / 0.6B dims
-  // (profiles/r03_skinny_routes.txt).  The row-group GEMV grows linearly in M (each group re-reads the weights), the
-  // tiled gemm_pf2_k is flat in M but has few blocks on narrow outputs, gemm_sk_k (every row in one block per column
-  // tile) reads the weights once but every block re-reads A:
-  //   outputs >= 4096 columns: gemm_sk_k at <= 48 rows of a <= 8 Mi-element weight (1.7B qkv 24 rows 11.5 -> 7.6 us,
-  //     48 rows 16.5 -> 10.7), else gemm_pf2_k (gate-up 80 rows 51.4 -> 16.2, 112 rows 87.6 -> 16.9; qkv 112 rows
-  //     35.1 -> 16.0);
-  //   narrower outputs: the row-group GEMV while M x N x K <= 400 Mi (1.7B o up to 100 rows: 80 rows 12.2 vs 13.0 us
-  //     on gemm_pf2_k; 1.7B down up to 33 rows: 24 rows 11.5 vs 16.9), else gemm_pf2_k with its narrow-output
-  //     split-K (1.7B down 80 rows 29.0 -> 16.9, 112 rows 37.7 -> 17.7; o 112 rows 15.5 -> 13.8, 200 rows 24.3 -> 13.5;
-  //     profiles/r03_skinny_routes.txt).
-  // QT_SKINNY=0 restores the round-2 rule (row-group GEMV up to 96 rows / 256 rows of <= 2048 columns).
-  p.sk = 0;
-  p.pf_small = 0;
-  static const int skinny_env = qt_knob("QT_SKINNY", 1);
-  const bool skinny = skinny_env != 0 && a->M > 16 && a->M <= 256 && a->taps == 0 && a->w_dtype == QT_BF16 &&
-                      a->a_dtype == QT_BF16 && a->K % 64 == 0 && a->a_index == nullptr && a->gamma == nullptr &&
-                      a->a_act == QT_AACT_NONE && a->snake_alpha == nullptr && a->lda % 8 == 0 &&
-                      ((size_t)a->A & 15) == 0 && a->N >= 32;
-  bool skinny_gemv = false;
-  if (skinny) {
-    if (a->N >= 4096) {
-      if (a->M <= sk_max_m() && (long long)a->N * a->K <= (8ll << 20)) p.sk = 1;
-      else p.pf_small = 1;
-    } else if ((long long)a->M * a->N * a->K <= (400ll << 20)) {
-      skinny_gemv = true;
-    } else {
-      p.pf_small = 1;
-    }
-  }
-  static const int rg_env = qt_knob("QT_GEMV_RG", 0);
-  if (a->M <= 16 && a->taps == 0 && a->w_dtype == QT_BF16 && a->K % KT == 0 && a->gamma == nullptr) {
-    // four groups of 2 rows for <= 64 tiles (CP down 6.5 -> 5.8 us; 128-tile shapes lose with four)
-    const int rg = rg_env > 0 ? rg_env : (a->M > 4 ? (ntl <= 64 ? 4 : (ntl <= 128 ? 2 : 1)) : 1);
-    if (rg > 1) {
-      p.mr = (a->M + rg - 1) / rg;
-      p.ks = 1;
-      // deep-K row-group shapes (the down projections) prefer 8 waves per block: talker down 9.4 -> 8.6,
-      // CP down 5.8 -> 5.6 us (o_proj / lm_head keep 16)
-      if (wpb_env <= 0 && ktl >= 96) p.wpb_max = 8;
-    }
-  } else if (skinny ? skinny_gemv
-                     : (a->M <= gemv_max_m() && (a->M <= 96 || a->N <= 2048) && a->taps == 0 && a->w_dtype == QT_BF16 &&
-                        a->K % KT == 0 && a->gamma == nullptr && a->a_act == QT_AACT_NONE &&
-                        a->snake_alpha == nullptr)) {
-    // skinny GEMM (17..96 rows, or up to gemv_max_m rows of a <= 2048-column output: the talker prefill of
-    // streaming-text prompts, short codec windows): the decode GEMV over row groups of 16 -- one block per (column
-    // tile, row group), the weight tile streamed from HBM once and re-read from L2 by the other row groups of its
-    // XCD.  Its time grows with the row groups; the tiled GEMMs' is flat in M but their grids are small for narrow
-    // outputs (tools/prefill_gemm_bench.py: M=80 o 29.6 -> 12.2 us, down 93.7 -> 29.0, qkv 36.0 -> 30.0, gate-up
-    // 79.0 -> 65.4; at M=160 gate-up 86 (igemm) vs 130, down 233 vs 48)
-    p.mr = gemv_mr();
-    p.ks = 1;
-    if (wpb_env <= 0 && ktl >= 96) p.wpb_max = 8;
-  }
-  const int w = a->w_dtype, o = a->o_dtype;
-  // out2 is written by the decode GEMV's epilogue (M <= 16, or the skinny row-group path above) and by gemm_pf_k
-  // (bf16-A prefill linears)
-  const bool pf = w == QT_BF16 && a->a_dtype == QT_BF16 && pf_route<bf16_t, bf16_t>(p);
-  if (p.out2 && !pf && !p.sk && (p.mr > 16 || a->K % KT != 0 || a->gamma != nullptr || a->a_act != QT_AACT_NONE))
-    return QT_ERR_ARG;
+  if (!a) return QT_ERR_ARG;
+  const GemmPlan pl = gemm_plan(*a, gemm_knobs());
+  if (pl.route == GemmRoute::NONE) return pl.err;
   hipStream_t s = (hipStream_t)stream;
-  const int ad = a->a_dtype;
-  if (w == QT_BF16 && ad == QT_F32 && o == QT_F32) return launch<bf16_t, float, float>(p, s);
-  if (w == QT_BF16 && ad == QT_BF16 && o == QT_BF16) return launch<bf16_t, bf16_t, bf16_t>(p, s);
-  if (w == QT_BF16 && ad == QT_BF16 && o == QT_F32) return launch<bf16_t, bf16_t, float>(p, s);
-  if (w == QT_BF16 && ad == QT_F32 && o == QT_BF16) return launch<bf16_t, float, bf16_t>(p, s);
-  if (w == QT_F32 && ad == QT_F32 && o == QT_F32) return launch<float, float, float>(p, s);
+  GemmRoute route = pl.route;
+  qt_gemm_args img;  // IM2COL: the linear call on the image
+  if (route == GemmRoute::IM2COL) {
+    // the image lives in the upper half of the caller's workspace (gemm_route.h im2col_applies)
+    img = qt_gemm_impl::im2col_linear_args(*a);
+    const GemmP q = gemm_params(*a, pl);
+    const long long n = (long long)a->M * a->taps * (a->cin_pad / 8);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (a->a_dtype == QT_BF16) hipLaunchKernelGGL(im2col_k<bf16_t>, grid, dim3(256), 0, s, q, (bf16_t*)img.A);
+    else hipLaunchKernelGGL(im2col_k<float>, grid, dim3(256), 0, s, q, (bf16_t*)img.A);
+    if (hipGetLastError() != hipSuccess) return QT_ERR_LAUNCH;
+    a = &img;
+    route = pl.inner;
+  }
+  const GemmP p = gemm_params(*a, pl);
+  const int w = a->w_dtype, ad = a->a_dtype, o = a->o_dtype;
+  if (w == QT_BF16 && ad == QT_F32 && o == QT_F32) return launch<bf16_t, float, float>(p, pl, route, s);
+  if (w == QT_BF16 && ad == QT_BF16 && o == QT_BF16) return launch<bf16_t, bf16_t, bf16_t>(p, pl, route, s);
+  if (w == QT_BF16 && ad == QT_BF16 && o == QT_F32) return launch<bf16_t, bf16_t, float>(p, pl, route, s);
+  if (w == QT_BF16 && ad == QT_F32 && o == QT_BF16) return launch<bf16_t, float, bf16_t>(p, pl, route, s);
+  if (w == QT_F32 && ad == QT_F32 && o == QT_F32) return launch<float, float, float>(p, pl, route, s);
   return QT_ERR_DTYPE;
 }
 

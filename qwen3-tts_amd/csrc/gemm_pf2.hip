@@ -24,7 +24,7 @@ using qt_gemm_impl::GemmP;
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
 typedef __attribute__((ext_vector_type(2))) float f32x2_t;
-constexpr int PF2_KS_MAX = 4;  // split-K factor bound (narrow outputs)
+using qt_gemm_impl::PF2_KS_MAX;  // split-K factor bound (narrow outputs)
 
 // SiLU from the hardware exp2 / reciprocal (v_exp_f32, v_rcp_f32: ~1 ulp each, 4 instructions): the IEEE
 // division + range-reduced expf of silu_f cost ~40 VALU per element, which made the SwiGLU epilogue of a
@@ -548,120 +548,45 @@ __global__ __launch_bounds__(WM * WN * 64) void gemm_pf2_k(GemmP p) {
   PF2_STAMP(2);
 }
 
-// split-K factor for a launch of nwg tiles: narrow (<= 2048-column) outputs whose tiles leave most CUs idle split K
-// (>= 16 stages of 64 per split; wide outputs measured slower split: 1.7B q/k/v at 80 rows 15.5 -> 17.9 us) when the caller's workspace holds the split records (QT_PF2_SPLIT=0 disables, measurement)
-template <int BM, int NTB, int WM, int WN>
-int pf2_splits(const GemmP& p, int nwg) {
-  static const int env = qt_knob("QT_PF2_SPLIT", 1);
-  const int S = p.Klog / 64;
-  if (!env || p.part == nullptr || p.cnt == nullptr || p.N > 2048 || nwg >= 192 || S < 32) return 1;
-  int ks = std::min({PF2_KS_MAX, 256 / nwg, S / 16});
-  constexpr int NW = WM * WN, MI = BM / WM / 16, CT = NTB / WN;
-  const long long rec = (long long)NW * MI * CT * 256 + WN * BM;
-  while (ks > 1 && (long long)nwg * ks * rec * 4 > p.part_bytes) --ks;
-  return std::max(ks, 1);
-}
-
 template <typename OT, int BM, int NTB, int NS, int WM = 2, int WN = 2, bool AFL = true, int PP = 0>
-void launch_pf2(const GemmP& p, hipStream_t s, int ks_pp = 1) {
+void launch_pf2(const GemmP& p, int ks, hipStream_t s) {  // ks: the plan's split-K factor (1 for 256-row tiles)
   const int ntl = (p.N + 15) / 16;
   const int nwg = ((p.M + BM - 1) / BM) * ((ntl + NTB - 1) / NTB);
-  const int ks = PP ? ks_pp : (BM <= 128 ? pf2_splits<BM, NTB, WM, WN>(p, nwg) : 1);
   const dim3 g(nwg, ks), b(WM * WN * 64);
   const bool plain = p.act == QT_ACT_NONE && p.bias == nullptr && p.colscale == nullptr;
-  if constexpr (BM <= 128) {
-    if (ks > 1) {  // narrow outputs: the split instantiations
-      if constexpr (std::is_same<OT, bf16_t>::value) {
-        if (plain && p.epi == QT_EPI_SWIGLU)
-          { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_SWIGLU, 0, true, PP>), g, b, 0, s, p); return; }
-      } else {
-        if (plain && p.epi == QT_EPI_STORE && !p.out2)
-          { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_STORE, 0, true, PP>), g, b, 0, s, p); return; }
-        if (plain && p.epi == QT_EPI_ADD && !p.out2)
-          { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_ADD, 0, true, PP>), g, b, 0, s, p); return; }
-        if (plain && p.epi == QT_EPI_ADD && p.out2)
-          { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_ADD_OUT2, 0, true, PP>), g, b, 0, s, p); return; }
-      }
-      hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_GENERIC, 0, true, PP>), g, b, 0, s, p);
-      return;
+  auto go = [&](auto split) {  // the epilogue form's instantiation, with or without the split-K merge
+    constexpr bool SP = decltype(split)::value;
+    if constexpr (std::is_same<OT, bf16_t>::value) {
+      if (plain && p.epi == QT_EPI_SWIGLU)
+        { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_SWIGLU, 0, SP, PP>), g, b, 0, s, p); return; }
+    } else {
+      if (plain && p.epi == QT_EPI_STORE && !p.out2)
+        { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_STORE, 0, SP, PP>), g, b, 0, s, p); return; }
+      if (plain && p.epi == QT_EPI_ADD && !p.out2)
+        { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_ADD, 0, SP, PP>), g, b, 0, s, p); return; }
+      if (plain && p.epi == QT_EPI_ADD && p.out2)
+        { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_ADD_OUT2, 0, SP, PP>), g, b, 0, s, p); return; }
     }
+    hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_GENERIC, 0, SP, PP>), g, b, 0, s, p);
+  };
+  if constexpr (BM <= 128) {  // narrow outputs: the split instantiations
+    if (ks > 1) return go(std::true_type{});
   }
-  if constexpr (std::is_same<OT, bf16_t>::value) {
-    if (plain && p.epi == QT_EPI_SWIGLU)
-      { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_SWIGLU, 0, false, PP>), g, b, 0, s, p); return; }
-  } else {
-    if (plain && p.epi == QT_EPI_STORE && !p.out2)
-      { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_STORE, 0, false, PP>), g, b, 0, s, p); return; }
-    if (plain && p.epi == QT_EPI_ADD && !p.out2)
-      { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_ADD, 0, false, PP>), g, b, 0, s, p); return; }
-    if (plain && p.epi == QT_EPI_ADD && p.out2)
-      { hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_ADD_OUT2, 0, false, PP>), g, b, 0, s, p); return; }
-  }
-  hipLaunchKernelGGL((gemm_pf2_k<OT, BM, NTB, NS, WM, WN, AFL, PF2_GENERIC, 0, false, PP>), g, b, 0, s, p);
+  go(std::false_type{});
 }
 
 #ifndef QT_PF2_PROBE
-// Tile configuration (QT_PF2_CFG = 3 / 4 / 9 / 11 / 21 / 22 / 23 forces one, measurement; 0 = chosen by shape).
-// tools/pf2_probe.hip timed every configuration on the 1.7B / 0.6B talker prefill shapes at M = 256 ... 4096
-// (profiles/r03_pf2_probe_sweep.txt, profiles/r06_pf2_pingpong_probe.txt): a block's time is nearly independent of M
-// and N (its loop runs K / 64 stages of a fixed tile), so launch time ~ ceil(blocks / resident slots) x block time,
-// and the best tile is the one whose block count quantises best onto the 256 CUs.  Block cycles per 2048 of K and
-// epilogue cycles below are those measurements; cfg 3 (72 KiB of LDS) runs 2 blocks per CU, the others 1.  The
-// ping-pong configurations (pp, 8 waves in two staggered groups) are considered from 256 rows (long prefills: voice
-// clone, non-streaming prompts); cfg 22 is cfg 21 with K split over two blocks (per-block K in its loop figure, its
-// epilogue the record merge), only for <= 2048-column outputs whose two-fold grid fits the 256 CUs.
-struct Pf2Cfg { int id, BM, BN, bpc; float loop1, loop2, epi; int pp, ks; };
-constexpr Pf2Cfg PF2_CFGS[] = {
-    {3, 128, 64, 2, 31000.f, 44000.f, 4000.f, 0, 1},   // 4 waves, wave tile 64 x 32
-    {11, 64, 96, 1, 28000.f, 28000.f, 3000.f, 0, 1},   // 4 waves, wave tile 32 x 48
-    {4, 256, 128, 1, 68000.f, 68000.f, 8000.f, 0, 1},  // 8 waves, wave tile 64 x 64
-    {9, 256, 160, 1, 76500.f, 76500.f, 9000.f, 1, 1},  // ping-pong, 8 waves, wave tile 64 x 80 (4-wave form: 95000)
-    {21, 128, 128, 1, 42600.f, 42600.f, 2500.f, 1, 1}, // ping-pong, 8 waves, wave tile 32 x 64
-    {22, 128, 128, 1, 45000.f, 45000.f, 9500.f, 1, 2}, // cfg 21, split-K 2
-    {23, 256, 256, 1, 97500.f, 97500.f, 10000.f, 1, 1}, // ping-pong, 8 waves, wave tile 64 x 128, 2 LDS stages
-};
-inline int pf2_cfg_env() {
-  static const int v = qt_knob("QT_PF2_CFG", 0);
-  return v;
-}
-inline bool pf2_split_fits(const GemmP& p, long long tiles, int ks) {  // cfg 22's records in the caller's workspace
-  constexpr long long rec = 8ll * 2 * 4 * 256 + 2 * 128;  // NW x MI x CT x 256 + WN x BM floats
-  return p.part != nullptr && p.cnt != nullptr && tiles <= 4096 && tiles * ks * rec * 4 <= p.part_bytes;
-}
-inline int pf2_pick(const GemmP& p) {
-  static const int pp_env = qt_knob("QT_PF2_PP", 1);  // 0: without the ping-pong configurations (A/B)
-  const int M = p.M, N = p.N, K = p.Klog;
-  int best = 3;
-  float best_t = 3.4e38f;
-  for (const Pf2Cfg& c : PF2_CFGS) {
-    if (c.pp && (M < 256 || !pp_env)) continue;
-    const long long tiles = (long long)((M + c.BM - 1) / c.BM) * ((N + c.BN - 1) / c.BN);
-    if (c.ks > 1 && (N > 2048 || tiles * c.ks > 256 || K / 64 < 32 || !pf2_split_fits(p, tiles, c.ks))) continue;
-    const long long blocks = tiles * c.ks;
-    const float kf = K / 2048.f / c.ks;
-    float t;
-    if (c.bpc == 2 && blocks > 256) t = (float)((blocks + 511) / 512) * (c.loop2 * kf + c.epi);
-    else t = (float)((blocks + 255) / 256) * (c.loop1 * kf + c.epi);
-    if (t < best_t) { best_t = t; best = c.id; }
-  }
-  return best;
-}
-
+// the tile configuration and split-K factor picked by the planner (gemm_route.h PF2_CFGS, pf2_pick, pf2_splits)
 template <typename OT>
-void launch_pf2_auto(const GemmP& p, hipStream_t s) {
-  int cfg = pf2_cfg_env();
-  if (cfg == 0) cfg = pf2_pick(p);
-  if (cfg == 22 && !pf2_split_fits(p, (long long)((p.M + 127) / 128) * ((p.N + 127) / 128), 2)) cfg = 21;
-  // (deeper pipelines of the two small-tile configurations -- 7 stages of 64 x 96, 6 of 128 x 64, one block per CU --
-  // measured slower at 24..680 rows: gate-up 160 rows 25.4 -> 37.9 us, qkv 680 rows 26.2 -> 37.1;
-  // profiles/r04_pf2_deep_ab.txt)
-  if (cfg == 4) launch_pf2<OT, 256, 8, 3, 4, 2>(p, s);
-  else if (cfg == 9) launch_pf2<OT, 256, 10, 3, 4, 2, true, 3>(p, s);
-  else if (cfg == 21) launch_pf2<OT, 128, 8, 4, 4, 2, true, 3>(p, s);
-  else if (cfg == 22) launch_pf2<OT, 128, 8, 4, 4, 2, true, 3>(p, s, 2);
-  else if (cfg == 23) launch_pf2<OT, 256, 16, 2, 4, 2, true, 3>(p, s);
-  else if (cfg == 11) launch_pf2<OT, 64, 6, 4, 2, 2>(p, s);
-  else launch_pf2<OT, 128, 4, 3>(p, s);
+void launch_pf2_cfg(const GemmP& p, int cfg, int ks, hipStream_t s) {
+  switch (cfg) {
+    case 4: launch_pf2<OT, 256, 8, 3, 4, 2>(p, ks, s); break;
+    case 9: launch_pf2<OT, 256, 10, 3, 4, 2, true, 3>(p, ks, s); break;
+    case 21: case 22: launch_pf2<OT, 128, 8, 4, 4, 2, true, 3>(p, ks, s); break;  // 22 = 21 with ks = 2
+    case 23: launch_pf2<OT, 256, 16, 2, 4, 2, true, 3>(p, ks, s); break;
+    case 11: launch_pf2<OT, 64, 6, 4, 2, 2>(p, ks, s); break;
+    default: launch_pf2<OT, 128, 4, 3>(p, ks, s); break;  // cfg 3
+  }
 }
 #endif  // QT_PF2_PROBE
 
@@ -669,7 +594,7 @@ void launch_pf2_auto(const GemmP& p, hipStream_t s) {
 
 #ifndef QT_PF2_PROBE
 namespace qt_gemm_impl {
-void launch_pf2_auto_f32(const GemmP& p, hipStream_t s) { launch_pf2_auto<float>(p, s); }
-void launch_pf2_auto_bf16(const GemmP& p, hipStream_t s) { launch_pf2_auto<bf16_t>(p, s); }
+void launch_pf2_f32(const GemmP& p, int cfg, int ks, hipStream_t s) { launch_pf2_cfg<float>(p, cfg, ks, s); }
+void launch_pf2_bf16(const GemmP& p, int cfg, int ks, hipStream_t s) { launch_pf2_cfg<bf16_t>(p, cfg, ks, s); }
 }  // namespace qt_gemm_impl
 #endif  // QT_PF2_PROBE

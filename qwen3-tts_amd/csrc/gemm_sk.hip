@@ -136,8 +136,8 @@ void launch_mi(const GemmP& p, hipStream_t s) {
 }
 
 template <typename OT>
-void launch_sk(const GemmP& p, hipStream_t s) {
-  switch ((p.M + 15) / 16) {  // qt_gemm routes 17..64 rows here
+void launch_sk(const GemmP& p, int mi, hipStream_t s) {
+  switch (mi) {  // qt_gemm routes 17..64 rows here
     case 2: launch_mi<OT, 2>(p, s); break;
     case 3: launch_mi<OT, 3>(p, s); break;
     default: launch_mi<OT, 4>(p, s); break;
@@ -147,6 +147,6 @@ void launch_sk(const GemmP& p, hipStream_t s) {
 }  // namespace
 
 namespace qt_gemm_impl {
-void launch_sk_f32(const GemmP& p, hipStream_t s) { launch_sk<float>(p, s); }
-void launch_sk_bf16(const GemmP& p, hipStream_t s) { launch_sk<bf16_t>(p, s); }
+void launch_sk_f32(const GemmP& p, int mi, hipStream_t s) { launch_sk<float>(p, mi, s); }
+void launch_sk_bf16(const GemmP& p, int mi, hipStream_t s) { launch_sk<bf16_t>(p, mi, s); }
 }  // namespace qt_gemm_impl

@@ -37,6 +37,17 @@ class GemmArgs(ctypes.Structure):
 
 GEMM_WS_MIN = 4 << 20  # QT_GEMM_WS_MIN
 
+# QT_ROUTE_*: the kernel family qt_gemm launches (csrc/gemm_route.h)
+(ROUTE_NONE, ROUTE_IM2COL, ROUTE_GEMV, ROUTE_SK, ROUTE_CONV_N1, ROUTE_WT_1x8, ROUTE_WT_2x8, ROUTE_WT_4x4, ROUTE_PF2,
+ ROUTE_PF, ROUTE_IGEMM) = range(11)
+ROUTE_NAMES = ["NONE", "IM2COL", "GEMV", "SK", "CONV_N1", "WT_1x8", "WT_2x8", "WT_4x4", "PF2", "PF", "IGEMM"]
+
+
+class GemmRouteInfo(ctypes.Structure):
+    """qt_gemm_route_info: the plan qt_gemm_route reports (inner = the linear route run on an im2col image)"""
+    _fields_ = [(n, c_int) for n in ("route", "inner", "ks", "mr", "wpb", "u", "fold", "nt_loads", "pf2_cfg", "pf2_ks",
+                                     "ntb", "mi", "sk_mi", "ws_split")]
+
 
 class QkvArgs(ctypes.Structure):
     _fields_ = [("R", c_int), ("Hq", c_int), ("Hkv", c_int), ("D", c_int), ("qkv", c_void_p), ("q_norm", c_void_p),
@@ -82,15 +93,6 @@ class CpStepArgs(ctypes.Structure):
                 ("ws_bytes", c_ll)]
 
 
-class TalkerStepArgs(ctypes.Structure):
-    _fields_ = [("R", c_int), ("n_layers", c_int), ("Lmax", c_int), ("eps", ctypes.c_float), ("wtab", c_void_p),
-                ("cos_tab", c_void_p), ("sin_tab", c_void_p), ("rope_pos", c_void_p), ("kv_pos", c_void_p),
-                ("row_start", c_void_p), ("row_batch", c_void_p), ("x", c_void_p), ("ldx", c_ll), ("ws", c_void_p),
-                ("ws_bytes", c_ll), ("first_layer", c_int), ("total_layers", c_int), ("qkv_in", c_void_p),
-                ("ldq_in", c_ll), ("qkv_out", c_void_p), ("ldq_out", c_ll), ("att_in", c_void_p), ("lda_in", c_ll),
-                ("att_out", c_void_p), ("lda_out", c_ll)]
-
-
 class TalkerTailArgs(ctypes.Structure):
     _fields_ = [("R", c_int), ("eps", ctypes.c_float), ("att", c_void_p), ("lda", c_ll), ("x", c_void_p), ("ldx", c_ll),
                 ("w_o", c_void_p), ("w_gu", c_void_p), ("w_down", c_void_p), ("w_qkv_next", c_void_p),
@@ -118,7 +120,7 @@ class SampleArgs(ctypes.Structure):
                 ("pick", c_void_p), ("rows", c_void_p)]
 
 
-EXPORTS = ["qt_gemm", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decode_attention", "qt_decode_attn_ws_bytes",
+EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decode_attention", "qt_decode_attn_ws_bytes",
            "qt_rmsnorm_rec", "qt_small_prefill_attention",
            "qt_decode_attn_oproj", "qt_attn_oproj_ws_bytes", "qt_attn_oproj_resident_blocks",
            "qt_cp_step", "qt_cp_prefill", "qt_cp_step_sampled", "qt_cp_step_ws_bytes", "qt_cp_step_supported", "qt_cp_step_dbg_bytes",
@@ -166,7 +168,7 @@ def load_library(path: str = LIB_PATH):
     BUILD_ID = bid
     P = c_void_p
     sig = {
-        "qt_gemm": [P, P], "qt_tile_weight": [P, c_int, c_int, c_int, P, P], "qt_qkv_post": [P, P],
+        "qt_gemm": [P, P], "qt_gemm_route": [P, P], "qt_tile_weight": [P, c_int, c_int, c_int, P, P], "qt_qkv_post": [P, P],
         "qt_attention": [P, P], "qt_decode_attention": [P, P], "qt_sample": [P, P],
         "qt_rmsnorm": [P, P, c_float, P, c_int, c_int, P],
         "qt_rmsnorm_rec": [P, P, c_float, P, c_int, c_int, P, c_ll, P, c_int, c_int, P],

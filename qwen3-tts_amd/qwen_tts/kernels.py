@@ -171,13 +171,10 @@ def active_workspace(device):
     return st[-1] if st else _WS.get(torch.device(device).index or 0)
 
 
-def gemm(A, W: Tiled, out, M, lda, ldo, *, a_dtype=None, o_dtype=None, gamma=None, eps=0.0, rms=False, colscale=None,
-         act=_hip.ACT_NONE, epi=_hip.EPI_STORE, a_index=None, conv=None, use_bias=True, splitk=0, snake=None,
-         a_act=_hip.AACT_NONE, out2=None, ldo2=None):
-    """conv = (t_in, t_out, t_off, dil) for implicit-conv weights.  splitk: 0 auto, 1 off, n forced
-    (decode GEMV; 0 / 1 also for gemm_pf2_k's narrow-output split-K; needs gemm_workspace(device) allocated).  snake = (alpha, inv_beta): SnakeBeta applied
-    to A per input channel inside the GEMM (fused codec activation).  out2: bf16 copy of the stored fp32 output
-    (M <= 16; the decode residual stream's shadow read by the next RMS-normalised GEMV)."""
+def _gemm_args(A, W: Tiled, out, M, lda, ldo, *, a_dtype=None, o_dtype=None, gamma=None, eps=0.0, rms=False,
+               colscale=None, act=_hip.ACT_NONE, epi=_hip.EPI_STORE, a_index=None, conv=None, use_bias=True, splitk=0,
+               snake=None, a_act=_hip.AACT_NONE, out2=None, ldo2=None):
+    """The qt_gemm_args of a gemm() / gemm_route() call (same parameters)."""
     a = _hip.GemmArgs()
     a.M, a.N, a.K = M, W.N, W.K
     a.a_dtype = _hip.dtype_code(a_dtype or A.dtype)
@@ -199,7 +196,29 @@ def gemm(A, W: Tiled, out, M, lda, ldo, *, a_dtype=None, o_dtype=None, gamma=Non
     if W.taps:
         t_in, t_out, t_off, dil = conv
         a.taps, a.dil, a.cin, a.cin_pad, a.t_in, a.t_out, a.t_off = W.taps, dil, W.cin, W.cin_pad, t_in, t_out, t_off
+    return a
+
+
+def gemm(A, W: Tiled, out, M, lda, ldo, *, a_dtype=None, o_dtype=None, gamma=None, eps=0.0, rms=False, colscale=None,
+         act=_hip.ACT_NONE, epi=_hip.EPI_STORE, a_index=None, conv=None, use_bias=True, splitk=0, snake=None,
+         a_act=_hip.AACT_NONE, out2=None, ldo2=None):
+    """conv = (t_in, t_out, t_off, dil) for implicit-conv weights.  splitk: 0 auto, 1 off, n forced
+    (decode GEMV; 0 / 1 also for gemm_pf2_k's narrow-output split-K; needs gemm_workspace(device) allocated).  snake = (alpha, inv_beta): SnakeBeta applied
+    to A per input channel inside the GEMM (fused codec activation).  out2: bf16 copy of the stored fp32 output
+    (M <= 16; the decode residual stream's shadow read by the next RMS-normalised GEMV)."""
+    a = _gemm_args(A, W, out, M, lda, ldo, a_dtype=a_dtype, o_dtype=o_dtype, gamma=gamma, eps=eps, rms=rms,
+                   colscale=colscale, act=act, epi=epi, a_index=a_index, conv=conv, use_bias=use_bias, splitk=splitk,
+                   snake=snake, a_act=a_act, out2=out2, ldo2=ldo2)
     check(_hip.lib().qt_gemm(ctypes.byref(a), stream()), "qt_gemm")
+
+
+def gemm_route(A, W: Tiled, out, M, lda, ldo, **kw) -> "_hip.GemmRouteInfo":
+    """The plan qt_gemm follows for the same call, gemm()'s parameters (qt_gemm_route: the route and its launch
+    decisions; nothing runs)."""
+    info = _hip.GemmRouteInfo()
+    check(_hip.lib().qt_gemm_route(ctypes.byref(_gemm_args(A, W, out, M, lda, ldo, **kw)), ctypes.byref(info)),
+          "qt_gemm_route")
+    return info
 
 
 def qkv_post(qkv, R, Hq, Hkv, D, q_norm, k_norm, eps, cos, sin, rope_pos, row_batch, kv_pos, q_out, kc, vc, Lmax):
@@ -286,13 +305,8 @@ def cp_step_supported(H, I, Hq, Hkv, D, n_layers, V) -> bool:
     return bool(_hip.lib().qt_cp_step_supported(H, I, Hq, Hkv, D, n_layers, V))
 
 
-def cp_step(layers, w_lm: "Tiled", x, qkv0, R, kcs, vcs, Lmax, const_pos, cos, sin, eps, logits, ws, sample=None):
-    """qt_cp_step: one code-predictor decode step (every layer + final norm + lm_head) in one persistent launch.
-    layers: the code predictor's _Layer objects (tiled qkv / o / gate-up / down, q_norm / k_norm); kcs / vcs: per-layer
-    bf16 caches [R][Hkv][Lmax][D]; x fp32 [R][H] input rows; qkv0 fp32 [R][qkv] layer-0 q/k/v rows; logits fp32 [R][V].
-    ws: zeroed uint8 scratch of cp_step_ws_bytes() kept across launches (word 0: the sticky hand-off error flag).
-    sample: qt_sample_args (sample(..., launch=False), with emb and emb2 tables) of the PREVIOUS step's token choice:
-    qt_cp_step_sampled runs it at the start of this launch and takes x / q/k/v from the chosen tokens' table rows."""
+def _cp_args(layers, w_lm: "Tiled", x, R, kcs, vcs, Lmax, const_pos, cos, sin, eps, logits, ws):
+    """qt_cp_step_args shared by cp_step and cp_prefill (everything but the layer-0 q/k/v rows)"""
     a = _hip.CpStepArgs()
     a.R, a.n_layers, a.Lmax, a.const_pos, a.V, a.eps = R, len(layers), Lmax, const_pos, w_lm.N, eps
     a.cos_tab, a.sin_tab = ptr(cos), ptr(sin)
@@ -302,9 +316,20 @@ def cp_step(layers, w_lm: "Tiled", x, qkv0, R, kcs, vcs, Lmax, const_pos, cos, s
         a.k_cache[i], a.v_cache[i] = ptr(kcs[i]), ptr(vcs[i])
     a.w_lm = ptr(w_lm.w)
     a.x, a.ldx = ptr(x), x.stride(0)
-    a.qkv0, a.ldq = ptr(qkv0), qkv0.stride(0)
     a.logits, a.ldl = ptr(logits), logits.stride(0)
     a.ws, a.ws_bytes = ptr(ws), ws.numel() * ws.element_size()
+    return a
+
+
+def cp_step(layers, w_lm: "Tiled", x, qkv0, R, kcs, vcs, Lmax, const_pos, cos, sin, eps, logits, ws, sample=None):
+    """qt_cp_step: one code-predictor decode step (every layer + final norm + lm_head) in one persistent launch.
+    layers: the code predictor's _Layer objects (tiled qkv / o / gate-up / down, q_norm / k_norm); kcs / vcs: per-layer
+    bf16 caches [R][Hkv][Lmax][D]; x fp32 [R][H] input rows; qkv0 fp32 [R][qkv] layer-0 q/k/v rows; logits fp32 [R][V].
+    ws: zeroed uint8 scratch of cp_step_ws_bytes() kept across launches (word 0: the sticky hand-off error flag).
+    sample: qt_sample_args (sample(..., launch=False), with emb and emb2 tables) of the PREVIOUS step's token choice:
+    qt_cp_step_sampled runs it at the start of this launch and takes x / q/k/v from the chosen tokens' table rows."""
+    a = _cp_args(layers, w_lm, x, R, kcs, vcs, Lmax, const_pos, cos, sin, eps, logits, ws)
+    a.qkv0, a.ldq = ptr(qkv0), qkv0.stride(0)
     if sample is not None:
         check(_hip.lib().qt_cp_step_sampled(ctypes.byref(a), ctypes.byref(sample), stream()), "qt_cp_step_sampled")
         return
@@ -315,17 +340,7 @@ def cp_prefill(layers, w_lm: "Tiled", x, R, kcs, vcs, Lmax, cos, sin, eps, logit
     """qt_cp_prefill: the code predictor's 2-token prefill (positions 0, 1 of R batch rows: x fp32 [2R][H], rows 2b,
     2b + 1) through every layer + lm_head[0] for position 1 (logits [R][V]) in one launch of the step engine; the
     keys / values land at cache positions 0, 1.  Same workspace as cp_step."""
-    a = _hip.CpStepArgs()
-    a.R, a.n_layers, a.Lmax, a.const_pos, a.V, a.eps = R, len(layers), Lmax, 0, w_lm.N, eps
-    a.cos_tab, a.sin_tab = ptr(cos), ptr(sin)
-    for i, L in enumerate(layers):
-        a.w_qkv[i], a.w_o[i], a.w_gu[i], a.w_down[i] = ptr(L.qkv.w), ptr(L.o.w), ptr(L.gu.w), ptr(L.down.w)
-        a.q_norm[i], a.k_norm[i] = ptr(L.q_norm), ptr(L.k_norm)
-        a.k_cache[i], a.v_cache[i] = ptr(kcs[i]), ptr(vcs[i])
-    a.w_lm = ptr(w_lm.w)
-    a.x, a.ldx = ptr(x), x.stride(0)
-    a.logits, a.ldl = ptr(logits), logits.stride(0)
-    a.ws, a.ws_bytes = ptr(ws), ws.numel() * ws.element_size()
+    a = _cp_args(layers, w_lm, x, R, kcs, vcs, Lmax, 0, cos, sin, eps, logits, ws)
     check(_hip.lib().qt_cp_prefill(ctypes.byref(a), stream()), "qt_cp_prefill")
 
 

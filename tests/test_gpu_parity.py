@@ -21,6 +21,13 @@ def _dev():
     return torch.device("cuda:0")
 
 
+def _route(Kn, *args, **kw):
+    """(route name, plan) of the Kn.gemm call with these arguments: qt_gemm_route, nothing is launched"""
+    from qwen_tts import _hip
+    info = Kn.gemm_route(*args, **kw)
+    return _hip.ROUTE_NAMES[info.route], info
+
+
 # ------------------------------------------------------------------------------------------ kernels
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("M,N,K", [(1, 64, 64), (8, 256, 512), (16, 96, 160), (37, 128, 96), (130, 48, 64)])
@@ -34,6 +41,8 @@ def test_gemm_linear(dtype, M, N, K):
     gamma = 1 + 0.1 * torch.randn(K, generator=g)
     t = Kn.tile_linear(W.to(dev), dtype, b.to(dev))
     out = torch.zeros(M, N, device=dev)
+    # a gamma vector keeps the call off the GEMV / tiled GEMMs: the gemm_wt fallbacks (1 x 8 to 16 rows, 4 x 4 above 32)
+    assert _route(Kn, A.to(dev), t, out, M, K, N, gamma=gamma.to(dev), eps=1e-6)[0] == ("WT_1x8" if M <= 16 else "WT_4x4")
     Kn.gemm(A.to(dev), t, out, M, K, N, gamma=gamma.to(dev), eps=1e-6)
     Wr = W.to(dtype).float()
     h = A * torch.rsqrt(A.pow(2).mean(-1, keepdim=True) + 1e-6) * gamma
@@ -67,9 +76,21 @@ def test_gemv_splitk_deterministic(dtype, M, N, K):
     t = Kn.tile_linear(W.to(dev), dtype, b)
     x0 = torch.randn(M, N, generator=g).to(dev)
     outs = {}
+    # the plan: bf16 weights run 5+ rows of <= 128 column tiles as row groups (4 groups to 64 tiles, else 2) without
+    # split-K; otherwise K splits by the forced factor (at most 16 and half the k tiles), and on its own only over
+    # deep K (more than 4 k tiles per wave) on < 256 column tiles, by 2
+    ntl, ktl = (N + 15) // 16, K // Kn.KT_OF[dtype]
+    rg = (4 if ntl <= 64 else 2 if ntl <= 128 else 1) if dtype == torch.bfloat16 and M > 4 else 1
+    wpb = 16 if ktl >= 48 else 8 if ktl >= 16 else 4
+    auto = 2 if -(-ktl // wpb) > 4 and ntl < 256 else 1
+    splits = set()
     for sk in (1, 2, 3, 4, 8, 0):
         for rms in (False, True):
             o = x0.clone()
+            name, plan = _route(Kn, A, t, o, M, K, N, rms=rms, eps=1e-6, epi=_hip.EPI_ADD, splitk=sk)
+            want_ks = 1 if rg > 1 else max(1, min(sk if sk else auto, 16, ktl // 2))
+            assert (name, plan.mr, plan.ks, plan.ws_split) == ("GEMV", -(-M // rg), want_ks, int(want_ks > 1))
+            splits.add(plan.ks)
             Kn.gemm(A, t, o, M, K, N, rms=rms, eps=1e-6, epi=_hip.EPI_ADD, splitk=sk)
             o2 = x0.clone()
             Kn.gemm(A, t, o2, M, K, N, rms=rms, eps=1e-6, epi=_hip.EPI_ADD, splitk=sk)
@@ -85,6 +106,7 @@ def test_gemv_splitk_deterministic(dtype, M, N, K):
         for sk in (1, 2, 3, 4, 8, 0):
             torch.testing.assert_close(outs[(sk, rms)], ref, atol=2e-4, rtol=2e-4)
             torch.testing.assert_close(outs[(sk, rms)], outs[(1, rms)], atol=2e-5, rtol=2e-5)
+    assert splits == ({1} if rg > 1 else {1, 2, 3, 4, 8})  # (row-group shapes never split: see the plan above)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -125,6 +147,9 @@ def test_gemm_causal_conv(cin, cout, k, dil):
     t = Kn.tile_conv(w.to(dev), b.to(dev), torch.float32, dil)
     xl = x.permute(0, 2, 1).contiguous().to(dev)
     out = torch.zeros(B * T, cout, device=dev)
+    # one output channel: conv_n1_k; the other fp32-weight convs of 74 rows: the 4 x 4 gemm_wt fallback
+    assert _route(Kn, xl, t, out, B * T, cin, cout, conv=(T, T, -(k - 1) * dil, dil))[0] == \
+        ("CONV_N1" if cout == 1 else "WT_4x4")
     Kn.gemm(xl, t, out, B * T, cin, cout, conv=(T, T, -(k - 1) * dil, dil))
     torch.testing.assert_close(out.view(B, T, cout).permute(0, 2, 1).cpu(), ref, atol=1e-4, rtol=1e-4)
 
@@ -144,7 +169,9 @@ def test_gemm_transposed_conv(cin, cout, s):
         t = Kn.tile_transconv(w.to(dev), b.to(dev), torch.float32, s)
         tout = T if k == s else T - 1
         out = torch.zeros(B * tout * s, cout, device=dev)
-        Kn.gemm(x.permute(0, 2, 1).contiguous().to(dev), t, out, B * tout, cin, s * cout, conv=(T, tout, 0, 1))
+        xl = x.permute(0, 2, 1).contiguous().to(dev)
+        assert _route(Kn, xl, t, out, B * tout, cin, s * cout, conv=(T, tout, 0, 1))[0] == "WT_2x8"  # 20 / 22 rows, fp32
+        Kn.gemm(xl, t, out, B * tout, cin, s * cout, conv=(T, tout, 0, 1))
         torch.testing.assert_close(out.view(B, tout * s, cout).permute(0, 2, 1).cpu(), ref, atol=1e-4, rtol=1e-4)
 
 
@@ -177,8 +204,10 @@ def test_igemm_conv_bf16(cin, cout, k, dil, T, snake):
     Kn.gemm_workspace(dev)
     for sk in (1, 0):  # splitk=1: the implicit GEMM; 0: windows of <= 1024 rows as im2col + the linear GEMMs
         out = res.permute(0, 2, 1).contiguous().reshape(B * T, cout).to(dev)
-        Kn.gemm(xl, t, out, B * T, cin, cout, conv=(T, T, -(k - 1) * dil, dil), epi=_hip.EPI_ADD,
-                snake=(al.to(dev), ib.to(dev)) if snake else None, splitk=sk)
+        kw = dict(conv=(T, T, -(k - 1) * dil, dil), epi=_hip.EPI_ADD,
+                  snake=(al.to(dev), ib.to(dev)) if snake else None, splitk=sk)
+        assert _route(Kn, xl, t, out, B * T, cin, cout, **kw)[0] == ("IGEMM" if sk == 1 or B * T > 1024 else "IM2COL")
+        Kn.gemm(xl, t, out, B * T, cin, cout, **kw)
         got = out.view(B, T, cout).permute(0, 2, 1).cpu()
         torch.testing.assert_close(got, ref + res, atol=2e-3, rtol=2e-3)
 
@@ -204,34 +233,45 @@ def test_short_window_conv_im2col(cin, cout, k, dil, T, B, elu, snake):
     outs = []
     for sk in (0, 1):
         out = torch.zeros(B * T, cout, device=dev)
-        Kn.gemm(xl, t, out, B * T, cin, cout, conv=(T, T, -(k - 1) * dil, dil), splitk=sk,
-                snake=(al.to(dev), ib.to(dev)) if snake else None, a_act=_hip.AACT_ELU if elu else _hip.AACT_NONE)
+        kw = dict(conv=(T, T, -(k - 1) * dil, dil), splitk=sk, snake=(al.to(dev), ib.to(dev)) if snake else None,
+                  a_act=_hip.AACT_ELU if elu else _hip.AACT_NONE)
+        name, plan = _route(Kn, xl, t, out, B * T, cin, cout, **kw)
+        assert name == ("IGEMM" if sk else "IM2COL")
+        if not sk:  # the 48-row window of 1536 x 7168 weights on the split-K prefill GEMM, the others on the GEMV
+            assert _hip.ROUTE_NAMES[plan.inner] == ("PF2" if cout == 1536 else "GEMV")
+        Kn.gemm(xl, t, out, B * T, cin, cout, **kw)
         outs.append(out.view(B, T, cout).permute(0, 2, 1).cpu())
     torch.testing.assert_close(outs[0], ref, atol=3e-3, rtol=3e-3)
     torch.testing.assert_close(outs[0], outs[1], atol=1e-4, rtol=1e-4)
 
 
-@pytest.mark.parametrize("s", [2, 5, 8])
-def test_igemm_transposed_conv_bf16(s):
+@pytest.mark.parametrize("s,T", [pytest.param(2, 150, id="2"), pytest.param(5, 150, id="5"), pytest.param(8, 150, id="8"),
+                                 (2, 514), (5, 514), (8, 514)])
+def test_igemm_transposed_conv_bf16(s, T):
+    """2-tap transposed conv on igemm_k.  The 298 rows of T = 150 stay on it only while no workspace has been allocated
+    in the process (with one, they are a short window: im2col + gemm_pf2_k); the 1026 rows of T = 514 always do."""
     from qwen_tts import kernels as Kn
     dev = _dev()
     g = torch.Generator().manual_seed(s + 100)
-    B, T, cin, cout = 2, 150, 64, 48
+    B, cin, cout = 2, 64, 48
     x = _bf(torch.randn(B, cin, T, generator=g))
     w, b = torch.randn(cin, cout, 2 * s, generator=g) * 0.05, torch.randn(cout, generator=g) * 0.1
     y = torch.nn.functional.conv_transpose1d(x, _bf(w), b, stride=s)
     ref = y[..., s:y.shape[-1] - s]
     t = Kn.tile_transconv(w.to(dev), b.to(dev), torch.bfloat16, s)
     out = torch.zeros(B * (T - 1) * s, cout, device=dev)
-    Kn.gemm(x.permute(0, 2, 1).contiguous().to(dev, torch.bfloat16), t, out, B * (T - 1), cin, s * cout,
-            conv=(T, T - 1, 0, 1))
+    xl = x.permute(0, 2, 1).contiguous().to(dev, torch.bfloat16)
+    short = T == 150 and Kn.active_workspace(dev) is not None
+    assert _route(Kn, xl, t, out, B * (T - 1), cin, s * cout, conv=(T, T - 1, 0, 1))[0] == ("IM2COL" if short else "IGEMM")
+    Kn.gemm(xl, t, out, B * (T - 1), cin, s * cout, conv=(T, T - 1, 0, 1))
     torch.testing.assert_close(out.view(B, (T - 1) * s, cout).permute(0, 2, 1).cpu(), ref, atol=2e-3, rtol=2e-3)
 
 
 @pytest.mark.parametrize("M,H,I", [(128, 256, 384), (300, 256, 384), (700, 288, 400), (1100, 512, 1024)])
 def test_igemm_linear_rms_swiglu_bf16(M, H, I):
-    """Large-M linears on the tiled path (gemm_pf_k: 128 x 128 / 128 x 64 tiles, ragged row / column / k tiles):
-    folded-gamma RMSNorm rows, SwiGLU epilogue, residual add."""
+    """Large-M linears on the tiled paths (ragged row / column / k tiles): folded-gamma RMSNorm rows + SwiGLU epilogue on
+    fp32 A (igemm_k), residual add on bf16 A (gemm_pf2_k; gemm_pf_k, 128 x 128 / 128 x 64 tiles, where K % 64 != 0:
+    the 700-row case).  The 128-row case is below both: its 768- and 256-column outputs run the row-group GEMV."""
     from qwen_tts import kernels as Kn, _hip
     dev = _dev()
     g = torch.Generator().manual_seed(M)
@@ -240,6 +280,8 @@ def test_igemm_linear_rms_swiglu_bf16(M, H, I):
     gate, up = torch.randn(I, H, generator=g) * 0.05, torch.randn(I, H, generator=g) * 0.05
     tgu = Kn.tile_swiglu(gate.to(dev), up.to(dev), torch.bfloat16, gamma=gamma.to(dev))
     h = torch.zeros(M, I, device=dev)
+    assert _route(Kn, x.to(dev), tgu, h, M, H, I, rms=True, eps=1e-6, epi=_hip.EPI_SWIGLU)[0] == \
+        ("GEMV" if M == 128 else "IGEMM")
     Kn.gemm(x.to(dev), tgu, h, M, H, I, rms=True, eps=1e-6, epi=_hip.EPI_SWIGLU)
     rs = torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + 1e-6)
     xa = _bf(x)
@@ -250,6 +292,7 @@ def test_igemm_linear_rms_swiglu_bf16(M, H, I):
     td = Kn.tile_linear(down.to(dev), torch.bfloat16)
     hb = h.to(torch.bfloat16)
     xr = x.to(dev).clone()
+    assert _route(Kn, hb, td, xr, M, I, H, epi=_hip.EPI_ADD)[0] == ("GEMV" if M == 128 else "PF" if I % 64 else "PF2")
     Kn.gemm(hb, td, xr, M, I, H, epi=_hip.EPI_ADD)
     torch.testing.assert_close(xr.cpu(), x + _bf(hb.cpu().float()) @ _bf(down).T, atol=2e-3, rtol=2e-3)
 
@@ -286,6 +329,7 @@ def test_prefill_gemm_pf2_bf16(M, N, K, mode):
         gamma = 1 + 0.1 * torch.randn(K, generator=g)
         t = Kn.tile_swiglu(gate.to(dev), up.to(dev), torch.bfloat16, gamma=gamma.to(dev))
         out = torch.zeros(M, I, device=dev, dtype=torch.bfloat16)
+        assert _route(Kn, A.to(dev), t, out, M, K, I, rms=True, eps=1e-6, epi=_hip.EPI_SWIGLU)[0] == "PF2"
         Kn.gemm(A.to(dev), t, out, M, K, I, rms=True, eps=1e-6, epi=_hip.EPI_SWIGLU)
         ref = torch.nn.functional.silu((Af @ _bf(gate * gamma).T) * rs) * ((Af @ _bf(up * gamma).T) * rs)
         torch.testing.assert_close(out.float().cpu(), ref, atol=1e-2, rtol=1e-2)
@@ -295,6 +339,7 @@ def test_prefill_gemm_pf2_bf16(M, N, K, mode):
         gamma = 1 + 0.1 * torch.randn(K, generator=g)
         t = Kn.tile_linear(W.to(dev), torch.bfloat16, gamma=gamma.to(dev))
         out = torch.zeros(M, N, device=dev)
+        assert _route(Kn, A.to(dev), t, out, M, K, N, rms=True, eps=1e-6)[0] == "PF2"
         Kn.gemm(A.to(dev), t, out, M, K, N, rms=True, eps=1e-6)
         ref = (Af @ _bf(W * gamma).T) * rs
         torch.testing.assert_close(out.cpu(), ref, atol=2e-3, rtol=2e-3)
@@ -304,6 +349,7 @@ def test_prefill_gemm_pf2_bf16(M, N, K, mode):
     x0 = torch.randn(M, N, generator=g)
     out = x0.to(dev).clone()
     o16 = None if mode == "add_noshadow" else torch.zeros(M, N, device=dev, dtype=torch.bfloat16)
+    assert _route(Kn, A.to(dev), t, out, M, K, N, epi=_hip.EPI_ADD, out2=o16)[0] == "PF2"
     Kn.gemm(A.to(dev), t, out, M, K, N, epi=_hip.EPI_ADD, out2=o16)
     ref = x0 + Af @ _bf(W).T + (0 if b is None else b)
     torch.testing.assert_close(out.cpu(), ref, atol=2e-3, rtol=2e-3)
@@ -334,6 +380,8 @@ def test_prefill_gemm_pf2_splitk(M, N, K, mode):
         outs = []
         for sk in (0, 0, 1):
             o = torch.zeros(M, N, device=dev)
+            name, plan = _route(Kn, A.to(dev), t, o, M, K, N, rms=True, eps=1e-6, splitk=sk)
+            assert name == "PF2" and (plan.pf2_ks > 1) == (sk == 0) == bool(plan.ws_split)
             Kn.gemm(A.to(dev), t, o, M, K, N, rms=True, eps=1e-6, splitk=sk)
             outs.append((o.cpu(), None))
     else:
@@ -344,6 +392,8 @@ def test_prefill_gemm_pf2_splitk(M, N, K, mode):
         for sk in (0, 0, 1):
             o = x0.to(dev).clone()
             o16 = torch.zeros(M, N, device=dev, dtype=torch.bfloat16) if mode == "add_shadow" else None
+            name, plan = _route(Kn, A.to(dev), t, o, M, K, N, epi=_hip.EPI_ADD, out2=o16, splitk=sk)
+            assert name == "PF2" and (plan.pf2_ks > 1) == (sk == 0) == bool(plan.ws_split)
             Kn.gemm(A.to(dev), t, o, M, K, N, epi=_hip.EPI_ADD, out2=o16, splitk=sk)
             outs.append((o.cpu(), None if o16 is None else o16.cpu()))
     torch.testing.assert_close(outs[0][0], ref, atol=2e-3, rtol=2e-3)
@@ -374,7 +424,7 @@ def test_skinny_gemm_bf16(M, N, K, mode):
         gate, up = torch.randn(I, K, generator=g) * 0.05, torch.randn(I, K, generator=g) * 0.05
         gamma = 1 + 0.1 * torch.randn(K, generator=g)
         t = Kn.tile_swiglu(gate.to(dev), up.to(dev), torch.bfloat16, gamma=gamma.to(dev))
-        run = lambda m: Kn.gemm(Ad, t, outs[m], abs(m), K, I, rms=True, eps=1e-6, epi=_hip.EPI_SWIGLU)  # noqa: E731
+        call = lambda f, m: f(Ad, t, outs[m], abs(m), K, I, rms=True, eps=1e-6, epi=_hip.EPI_SWIGLU)  # noqa: E731
         outs = {m: torch.zeros(abs(m), I, device=dev, dtype=torch.bfloat16) for m in (M, -17)}
         ref = torch.nn.functional.silu((Af @ _bf(gate * gamma).T) * rs) * ((Af @ _bf(up * gamma).T) * rs)
         tol = 1e-2
@@ -383,7 +433,7 @@ def test_skinny_gemm_bf16(M, N, K, mode):
         gamma = 1 + 0.1 * torch.randn(K, generator=g)
         t = Kn.tile_linear(W.to(dev), torch.bfloat16, gamma=gamma.to(dev))
         outs = {m: torch.zeros(abs(m), N, device=dev) for m in (M, -17)}
-        run = lambda m: Kn.gemm(Ad, t, outs[m], abs(m), K, N, rms=True, eps=1e-6)  # noqa: E731
+        call = lambda f, m: f(Ad, t, outs[m], abs(m), K, N, rms=True, eps=1e-6)  # noqa: E731
         ref = (Af @ _bf(W * gamma).T) * rs
         tol = 2e-3
     else:
@@ -394,20 +444,21 @@ def test_skinny_gemm_bf16(M, N, K, mode):
         outs = {m: x0[:abs(m)].to(dev).clone() for m in (M, -17)}
         o16 = {m: (None if mode == "add_noshadow" else torch.zeros(abs(m), N, device=dev, dtype=torch.bfloat16))
                for m in (M, -17)}
-        run = lambda m: Kn.gemm(Ad, t, outs[m], abs(m), K, N, epi=_hip.EPI_ADD, out2=o16[m])  # noqa: E731
+        call = lambda f, m: f(Ad, t, outs[m], abs(m), K, N, epi=_hip.EPI_ADD, out2=o16[m])  # noqa: E731
         ref = x0 + Af @ _bf(W).T + (0 if b is None else b)
         tol = 2e-3
-    run(M)
-    run(-17)  # the first 17 rows alone (key -17)
-    got = outs[M].float().cpu()
-    torch.testing.assert_close(got, ref, atol=tol, rtol=tol)
-    # qt_gemm's 17..256-row rule (gemm.hip): gemm_sk_k / row-group GEMV rows do not depend on M
+    # qt_gemm's 17..256-row rule (gemm_route.h): gemm_sk_k / row-group GEMV rows do not depend on M
     nw = N
 
     def route(m):
         if nw >= 4096:
             return "sk" if m <= 48 and nw * K <= (8 << 20) else "pf2"
         return "gemv" if m * nw * K <= (400 << 20) else "pf2"
+    for m in (M, -17):  # the first 17 rows alone (key -17)
+        assert _hip.ROUTE_NAMES[call(Kn.gemm_route, m).route] == route(abs(m)).upper()
+        call(Kn.gemm, m)
+    got = outs[M].float().cpu()
+    torch.testing.assert_close(got, ref, atol=tol, rtol=tol)
     if route(M) == route(17) != "pf2":
         assert torch.equal(outs[-17].float().cpu(), got[:17]), "row results depend on M"
     if mode in ("add", "add_plain"):

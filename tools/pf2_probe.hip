@@ -43,7 +43,7 @@ void run(const char* name, GemmP p, int reps) {
     CK(hipMalloc(&g_cnt, 4096 * 4)); CK(hipMemset(g_cnt, 0, 4096 * 4));
     CK(hipMalloc(&g_part, PART_BYTES));
   }
-  p.cnt = g_cnt; p.part = g_part; p.part_bytes = PART_BYTES;
+  p.cnt = g_cnt; p.part = g_part;
   {  // the split records must fit the partial buffer (and the counters their array)
     constexpr long long REC = 8ll * (BM / WM / 16) * (NTB / WN) * 256 + WN * BM;
     const long long tiles = (long long)((p.M + BM - 1) / BM) * (((p.N + 15) / 16 + NTB - 1) / NTB);
