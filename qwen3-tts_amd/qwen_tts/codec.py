@@ -208,6 +208,10 @@ class CodecDecoder:
         to return its state slot (and the slot's captured feed graphs) to the pool."""
         return CodecStream(self, B, max_frames)
 
+    def row_stream(self, B: int, max_frames: int, n_max: int = 8) -> "RowCodecStream":
+        """stream() with a clock per batch row (rows begin, idle and end independently; feeds of up to n_max frames)."""
+        return RowCodecStream(self, B, max_frames, n_max)
+
     def _acquire_slot(self, B, max_frames) -> "_StreamSlot":
         pool = self._slots.setdefault((B, max_frames), [])
         for sl in pool:
@@ -465,5 +469,228 @@ class CodecStream:
         with torch.cuda.stream(side):
             with torch.cuda.graph(g, stream=side):
                 out = self._compute(cin, n, first)
+        torch.cuda.current_stream(self.dec.dev).wait_stream(side)
+        return g, cin, out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# per-row incremental decode: every batch row its own request clock (continuous batching, TTSModel.serve_stream)
+class _RowStreamSlot:
+    """State of one per-row incremental decode, pooled per (B, max_frames, n_max): K/V caches of max_frames + n_max
+    positions (a filler row's K/V lands past its row's clock, never on a valid slot), every stage's input history,
+    the per-row frame clocks and the row table (nrow, begin) as static device buffers, the feed graphs keyed by the
+    feed capacity n alone."""
+
+    def __init__(self, dec: "CodecDecoder", B: int, max_frames: int, n_max: int):
+        dev = dec.dev
+        self.Lm = max_frames + n_max
+        self.kc = [torch.zeros(B, dec.kvh, self.Lm, dec.hd, dtype=torch.float32, device=dev) for _ in dec.layers]
+        self.vc = [torch.zeros_like(k) for k in self.kc]
+        self.nf_dev = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.rows = torch.zeros(2, B, dtype=torch.int32, device=dev)
+        self.meta_b = {}    # n -> row_batch [B*n]
+        self.hist = {}      # stage key -> [B][rows][C]
+        self.graphs = {}    # n -> (graph, static codes input, static pcm output)
+        self.uses = {}
+        self.busy = False
+        self.ws = K.new_workspace(dev)
+
+
+class RowCodecStream:
+    """CodecStream with a clock per batch row: feed(codes [B, n, 16], nrow [B], begin [B]) -> pcm [B, 1920 n].
+
+    Row b consumes its first nrow[b] <= n frames (the rest is filler: computed, never entering any state); with
+    begin[b] it first restarts from the zero state, whatever the slot held (a request begins with nrow[b] >= 1:
+    begin with nrow 0 only resets the row, which must then begin again).  Shapes never depend on row state: every
+    transposed conv runs CodecStream's non-first form ([history | x] in, n rows out), so a beginning row's output of
+    decoder block i starts with s_i = (s_{i-1} + 1) r_i spurious rows (s_0 = 0: 8 / 45 / 184 / 555 at rates 8, 5, 4,
+    3 -- 555 is the one-shot's lookahead).  Every later stage's input window reads them as zeros (qt_stream_window's
+    `head`), which is the one-shot's zero padding because SnakeBeta(0) = 0.  The valid samples of row b in a feed
+    are [555 if begin[b] else 0, 1920 nrow[b]); concatenated from a begin on they equal forward(codes_b)[:1920 F -
+    555].  The row table is a static device buffer uploaded before the feed, so one graph per capacity n serves every
+    mix of beginning, continuing, idle and ragged rows."""
+
+    def __init__(self, dec: "CodecDecoder", B: int, max_frames: int, n_max: int = 8):
+        self.dec, self.B, self.max_frames, self.n_max = dec, B, max_frames, n_max
+        if dec.cos.shape[0] < max_frames + n_max:  # old tables stay alive: captured feed graphs read them
+            dec._old_rope = getattr(dec, "_old_rope", []) + [(dec.cos, dec.sin)]
+            dec.cos, dec.sin = K.rope_tables(dec.hd, dec.d["rope_theta"], max_frames + n_max + 64, dec.dev)
+        if not hasattr(dec, "_row_slots"):
+            dec._row_slots = {}  # (B, max_frames, n_max) -> [_RowStreamSlot]
+        pool = dec._row_slots.setdefault((B, max_frames, n_max), [])
+        self.slot = next((sl for sl in pool if not sl.busy), None)
+        if self.slot is None:
+            self.slot = _RowStreamSlot(dec, B, max_frames, n_max)
+            pool.append(self.slot)
+        self.slot.busy = True
+        self.nf = [0] * B  # frames on each row's clock
+        self.live = [False] * B  # the row has begun on this stream (until then the slot's state is another stream's)
+        # spurious leading rows of a beginning row after each decoder block
+        self.heads = [0]
+        rpf = math.prod(u["f"] for u in dec.ups)
+        for blk in dec.blocks:
+            self.heads.append((self.heads[-1] + 1) * blk["r"])
+            rpf *= blk["r"]
+            # the feed in which a row begins (nrow >= 1) must cover its spurious rows: later feeds do not mask
+            assert self.heads[-1] <= rpf, (self.heads, rpf)
+
+    def close(self):
+        if self.slot is not None:
+            self.slot.busy = False
+            self.slot = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- stages ----------------------------------------------------------------------------------------
+    def _window(self, key, x, L, C, H, rpf, head):
+        """[history | x] of one stage per the row table, the history advanced by each row's own rows."""
+        B, dev = self.B, self.dec.dev
+        h = self.slot.hist.get(key)
+        if h is None:  # first use on this slot (eager, never inside a capture)
+            h = self.slot.hist[key] = torch.zeros(B, H, C, dtype=x.dtype, device=dev)
+        xin = torch.empty(B, H + L, C, dtype=x.dtype, device=dev)
+        K.stream_window(h, x, xin, B, H, L, C, rpf, head, self.slot.rows)
+        return xin
+
+    def _causal(self, key, x, L, Wt, cin, rpf, head, out=None, epi=_hip.EPI_STORE, snake=None):
+        dec, B = self.dec, self.B
+        H = (Wt.taps - 1) * getattr(Wt, "dil", 1)
+        # (a 1-tap conv keeps no state and maps a spurious row to a spurious row: no window)
+        xin = self._window(key, x, L, cin, H, rpf, head) if H else x
+        if out is None:
+            out = torch.empty(B * L, Wt.N, dtype=dec.adt, device=dec.dev)
+        dec._conv(xin, Wt, B, H + L, L, 0, out, cin, epi=epi, snake=snake)
+        return out
+
+    def _transformer(self, h, n):
+        dec, B, dev, sl = self.dec, self.B, self.dec.dev, self.slot
+        R = B * n
+        hid, nh, nkv, D = dec.hid, dec.heads, dec.kvh, dec.hd
+        x = torch.empty(R, dec.inp.N, dtype=torch.float32, device=dev)
+        K.gemm(h, dec.inp, x, R, dec.lat, dec.inp.N)
+        pos = torch.empty(R, dtype=torch.int32, device=dev)
+        row_len = torch.empty_like(pos)
+        K.stream_rows(sl.nf_dev, sl.rows, B, n, pos, row_len)
+        meta_b = sl.meta_b[n]
+        row_start = torch.zeros_like(pos)
+        qkv_w = (nh + 2 * nkv) * D
+        qkv = torch.empty(R, qkv_w, dtype=torch.float32, device=dev)
+        q = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
+        att = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
+        inter = dec.d["intermediate_size"]
+        hmid = torch.empty(R, inter, dtype=torch.float32, device=dev)
+        eps, win, Lm = dec.d["rms_norm_eps"], dec.d["sliding_window"], sl.Lm
+        for L, kc, vc in zip(dec.layers, sl.kc, sl.vc):
+            K.gemm(x, L["qkv"], qkv, R, hid, qkv_w, rms=True, eps=eps)
+            K.qkv_post(qkv, R, nh, nkv, D, None, None, eps, dec.cos, dec.sin, pos, meta_b, pos, q, kc, vc, Lm)
+            K.attention(q, R, nh, nkv, D, kc, vc, Lm, meta_b, row_start, row_len, att, win, window=win)
+            K.gemm(att, L["o"], x, R, nh * D, hid, colscale=L["ls1"], epi=_hip.EPI_ADD)
+            K.gemm(x, L["gu"], hmid, R, hid, inter, rms=True, eps=eps, epi=_hip.EPI_SWIGLU)
+            K.gemm(hmid, L["down"], x, R, inter, hid, colscale=L["ls2"], epi=_hip.EPI_ADD)
+        y = torch.empty(R, dec.lat, dtype=dec.adt, device=dev)
+        K.gemm(x, dec.outp, y, R, hid, dec.lat, rms=True, eps=eps)
+        return y
+
+    def _compute(self, codes: torch.Tensor, n: int):
+        """The device work of one feed of capacity n (graph-capturable: row state comes from the slot's row table
+        and clocks); returns the clamped PCM rows [B][1920 n]."""
+        dec, B, dev, adt = self.dec, self.B, self.dec.dev, self.dec.adt
+        o1 = torch.empty(B * n, dec.cb_dim, dtype=torch.float32, device=dev)
+        o2 = torch.empty_like(o1)
+        K.rvq_gather(dec.tables, codes.shape[2], 1, dec.tables.shape[1], dec.cb_dim, codes, B, n, o1, o2)
+        cd = dec.proj_first.N
+        h = torch.empty(B * n, cd, dtype=adt, device=dev)
+        K.gemm(o1, dec.proj_first, h, B * n, dec.cb_dim, cd)
+        K.gemm(o2, dec.proj_rest, h, B * n, dec.cb_dim, cd, epi=_hip.EPI_ADD)
+        x = self._causal("pre", h, n, dec.pre_conv, cd, 1, 0)
+        x = self._transformer(x, n)
+        L, C = n, dec.lat
+        for i, u in enumerate(dec.ups):
+            f = u["f"]
+            y = torch.empty(B * L * f, C, dtype=adt, device=dev)
+            dec._conv(x, u["tconv"], B, L, L, 0, y, C)
+            L *= f
+            Hd = u["dw_w"].shape[1] - 1
+            yin = self._window(f"dw{i}", y, L, C, Hd, L // n, 0)
+            z = torch.empty_like(yin)
+            K.dwconv_ln(yin, B, Hd + L, C, u["dw_w"], u["dw_b"], u["ln_w"], u["ln_b"], 1e-6, z)
+            z = z[:, Hd:].contiguous()
+            hmid = torch.empty(B * L, u["pw1"].N, dtype=adt, device=dev)
+            K.gemm(z, u["pw1"], hmid, B * L, C, u["pw1"].N, act=_hip.ACT_GELU)
+            K.gemm(hmid, u["pw2"], y, B * L, u["pw1"].N, C, colscale=u["gamma"], epi=_hip.EPI_ADD)
+            x = y
+        x = self._causal("conv0", x, L, dec.conv0, C, L // n, 0)
+        C = dec.d["decoder_dim"]
+        for bi, blk in enumerate(dec.blocks):
+            r, cout = blk["r"], blk["cout"]
+            # 2-tap transposed conv, always in its continuing form: [last input row | x] -> L rows of r samples
+            xin = self._window(f"t{bi}", x, L, C, 1, L // n, self.heads[bi])
+            y = torch.empty(B * L, blk["tconv"].N, dtype=adt, device=dev)
+            dec._conv(xin, blk["tconv"], B, L + 1, L, 0, y, C, snake=blk["s"])
+            L, C, x = L * r, cout, y
+            hd = self.heads[bi + 1]
+            for ui, un in enumerate(blk["units"]):
+                bb = self._causal(f"u{bi}.{ui}", x, L, un["c1"], C, L // n, hd, snake=un["s1"])
+                self._causal(f"v{bi}.{ui}", bb, L, un["c2"], C, L // n, hd, out=x, epi=_hip.EPI_ADD, snake=un["s2"])
+        out = self._causal("last", x, L, dec.conv_last, C, L // n, self.heads[-1],
+                           out=torch.empty(B * L, dec.conv_last.N, dtype=torch.float32, device=dev), snake=dec.s_last)
+        pcm = out[:, 0].contiguous()
+        K.clamp_pcm(pcm, pcm.numel(), pcm)
+        return pcm.view(B, L)
+
+    def feed(self, codes: torch.Tensor, nrow, begin) -> torch.Tensor:
+        """codes int [B, n, 16]; nrow[b] <= n frames of row b are consumed, after a restart when begin[b].  Returns
+        pcm fp32 [B, 1920 n] (valid until the next feed of this capacity); row b's valid samples are
+        [555 if begin[b] else 0, 1920 nrow[b])."""
+        dec, B, dev, slot = self.dec, self.B, self.dec.dev, self.slot
+        n = codes.shape[1]
+        nrow, begin = [int(v) for v in nrow], [int(bool(v)) for v in begin]
+        if codes.shape[0] != B or len(nrow) != B or len(begin) != B or not 0 < n <= self.n_max:
+            raise ValueError(f"RowCodecStream({B} rows, capacity {self.n_max}): got codes {tuple(codes.shape)}")
+        for b in range(B):
+            if not 0 <= nrow[b] <= n:
+                raise ValueError(f"row {b}: nrow {nrow[b]} outside [0, {n}]")
+            if nrow[b] and not (begin[b] or self.live[b]):
+                raise ValueError(f"row {b} has not begun on this stream")
+            if (0 if begin[b] else self.nf[b]) + nrow[b] > self.max_frames:
+                raise ValueError(f"RowCodecStream holds {self.max_frames} frames per row; row {b} has "
+                                 f"{0 if begin[b] else self.nf[b]}, {nrow[b]} more given")
+        codes = codes.to(dev, torch.int32).contiguous()
+        # a row that never began on this stream sits on another stream's clock and state: it begins with no frames
+        # (clock 0, zero state) until its own begin
+        tab = torch.tensor([nrow, [int(begin[b] or not self.live[b]) for b in range(B)]], dtype=torch.int32)
+        slot.rows.copy_(tab.pin_memory(), non_blocking=True)
+        if n not in slot.meta_b:
+            slot.meta_b[n] = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(n)
+        g = slot.graphs.get(n)
+        if g is not None:
+            g[1].copy_(codes)
+            g[0].replay()
+            pcm = g[2]
+        else:
+            with K.use_workspace(slot.ws):
+                pcm = self._compute(codes, n)
+                slot.uses[n] = slot.uses.get(n, 0) + 1
+                if CODEC_GRAPH and slot.uses[n] >= 2:
+                    slot.graphs[n] = self._capture(codes, n)
+        for b in range(B):
+            if begin[b]:  # (the spurious rows are masked in the beginning feed only: a begin without frames is a reset)
+                self.nf[b], self.live[b] = 0, nrow[b] > 0
+            self.nf[b] += nrow[b]
+        return pcm
+
+    def _capture(self, codes, n):
+        # capturing executes nothing: the slot state is left as the eager feed left it
+        cin = codes.clone()
+        side = torch.cuda.Stream(device=self.dec.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dec.dev))
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side):
+            with torch.cuda.graph(g, stream=side):
+                out = self._compute(cin, n)
         torch.cuda.current_stream(self.dec.dev).wait_stream(side)
         return g, cin, out

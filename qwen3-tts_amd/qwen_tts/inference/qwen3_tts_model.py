@@ -393,7 +393,7 @@ class Qwen3TTSModel:
 
     @torch.no_grad()
     def stream(self, text, speaker=None, language=None, instruct=None, non_streaming_mode=True,
-               first_chunk_frames=1, chunk_frames=48, left_context=None, **kwargs):
+               first_chunk_frames=1, chunk_frames=48, left_context=None, max_batch=None, **kwargs):
         """New surface (no reference counterpart): streaming custom-voice generation.
         Yields (utterance index, pcm chunk np.float32, sample rate, is_last) while the batch decodes: the first
         chunk arrives after prefill + `first_chunk_frames` decode frames (1 frame: 1365 samples = 57 ms of audio,
@@ -401,13 +401,15 @@ class Qwen3TTSModel:
         (each chunk's audio outlasts the generation of the next).  Per utterance the
         chunks concatenate to the one-shot generate_custom_voice() length and equal its PCM up to fp summation order
         (a stateful incremental codec decode; codes are identical -- see TTSModel.stream for the chunk rule and the
-        stateless `left_context` form)."""
+        stateless `left_context` form).  max_batch: with more utterances than max_batch, they stream through
+        max_batch continuously batched rows instead (TTSModel.serve_stream): a row is refilled with the next
+        utterance as soon as its own ends, and every utterance has a first chunk of its own."""
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
         sr = self.model.speech_tokenizer.get_output_sample_rate()
         for i, pcm, last in self.model.stream(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                               speakers=speakers, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
-                                              left_context=left_context,
+                                              left_context=left_context, max_batch=max_batch,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, pcm.to(torch.float32).cpu().numpy(), sr, last
 

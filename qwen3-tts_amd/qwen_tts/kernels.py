@@ -468,6 +468,18 @@ def advance_rows(counters, B, nfields, cap):
     check(_hip.lib().qt_advance_rows(ptr(counters), B, nfields, cap, stream()), "qt_advance_rows")
 
 
+def stream_window(hist, x, xin, B, H, n, C, rows_per_frame, head, rows):
+    """xin [B][H+n][C] = [hist | x] per the row table rows [2][B] (nrow, begin), then hist = xin[:, m_b:m_b + H]
+    (m_b = nrow[b] * rows_per_frame); a beginning row reads zero history and zeros for its first `head` rows."""
+    check(_hip.lib().qt_stream_window(ptr(hist), ptr(x), ptr(xin), _hip.dtype_code(x.dtype), B, H, n, C,
+                                      rows_per_frame, head, ptr(rows), stream()), "qt_stream_window")
+
+
+def stream_rows(nf, rows, B, n, pos, row_len):
+    """Per-row codec clock: pos [B][n] = (begin ? 0 : nf[b]) + j, row_len = pos + 1, nf[b] advances by nrow[b]."""
+    check(_hip.lib().qt_stream_rows(ptr(nf), ptr(rows), B, n, ptr(pos), ptr(row_len), stream()), "qt_stream_rows")
+
+
 def rvq_gather(tables, Q, n_first, cb, dim, codes, B, T, o1, o2):
     check(_hip.lib().qt_rvq_gather(ptr(tables), Q, n_first, cb, dim, ptr(codes), B, T, ptr(o1), ptr(o2), stream()),
           "qt_rvq_gather")

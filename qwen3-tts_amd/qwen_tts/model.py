@@ -342,7 +342,7 @@ class TTSModel:
                speakers=None, non_streaming_mode=False, max_new_tokens=4096, do_sample=True, top_k=50, top_p=1.0,
                temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
-               first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, **kwargs):
+               first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None, **kwargs):
         """Streaming generation (the reference has none): yields (row, pcm, last) as frames finish.
 
         Per row the chunks concatenate to the one-shot generate() + decode() PCM (Z:259-365): the reference
@@ -355,7 +355,20 @@ class TTSModel:
         stateless form instead (windows [s, e) within a reference chunk, one lookahead frame), re-decoded from
         min(its chunk's start, left_context frames back) -- 325 reproduces the reference, less is approximate (in
         fp32 150 frames -> rel-L2 1e-6, 72 -> 7e-4, 25 -> 2e-2; tools/stream_fidelity.py).  Codes are identical to
-        generate().  pcm is a 1-D fp32 device tensor of 24 kHz samples."""
+        generate().  pcm is a 1-D fp32 device tensor of 24 kHz samples.
+
+        max_batch: with more requests than max_batch, stream them by continuous batching through max_batch batch
+        rows (serve_stream(): a row is refilled as soon as its request ends; chunk_frames then defaults to 8)."""
+        if max_batch is not None and input_ids is not None and len(input_ids) > int(max_batch):
+            if left_context is not None:
+                raise NotImplementedError("stream(left_context=...) with max_batch: use the default stateful stream")
+            yield from self.serve_stream(
+                input_ids, instruct_ids, ref_ids, voice_clone_prompt, languages, speakers, non_streaming_mode,
+                max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
+                subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed,
+                max_batch=max_batch, first_chunk_frames=first_chunk_frames,
+                chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, **kwargs)
+            return
         dec = self.speech_tokenizer.model
         up = dec.total_upsample
         RC, RX = self.REF_CHUNK, self.REF_CTX
@@ -445,6 +458,102 @@ class TTSModel:
                         yield b, torch.zeros(0, device=codes.device), True
             if all(done):
                 break
+
+    @torch.no_grad()
+    def serve_stream(self, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None, languages=None,
+                     speakers=None, non_streaming_mode=False, max_new_tokens=4096, do_sample=True, top_k=50,
+                     top_p=1.0, temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
+                     subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False,
+                     seed=None, max_batch=8, first_chunk_frames=1, chunk_frames=8, use_graph=True, philox_ids=None,
+                     frame_caps=None, **kwargs):
+        """Streaming from the continuously batched route (the reference has neither): the requests are
+        decoded through max_batch batch rows as generate(max_batch=...) decodes them, and each request's audio
+        leaves as it is generated -- yields (request index, pcm, last).
+
+        Per request the chunks concatenate to Qwen3TTSTokenizer.decode of that request's codes alone (300-frame
+        reference chunks with 25 frames of left context, each chunk's last 555 samples dropped, 1920 x #nonzero-cb0
+        samples kept), and the codes are generate(max_batch=...)'s.  The talker reports progress every chunk_frames
+        frame replays, and first_chunk_frames after a row's refill (TalkerEngine.serve_iter); the new frames of
+        every row go through one per-row incremental codec feed (codec.RowCodecStream: a refilled row begins, the
+        others continue, idle ones ride along), so a refilled request has a first packet of its own.  A row that
+        reaches the end of a reference chunk restarts on the chunk's 25 context frames (their output discarded)
+        while the other rows carry on.  The sampling parameters take per-request lists as in generate().  Voice-clone
+        prompts that carry reference codes (ICL) are not supported here; x-vector-only prompts are."""
+        refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
+        if refs is not None and any(r is not None for r in refs):
+            raise NotImplementedError("serve_stream() / stream(max_batch=...) with voice-clone reference codes (ICL): "
+                                      "use stream() without max_batch, or x-vector-only prompts")
+        dec = self.speech_tokenizer.model
+        up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
+        emb, mask, trail, pad = self.build_prompts(input_ids, languages, speakers, instruct_ids, non_streaming_mode,
+                                                   voice_clone_prompt, ref_ids)
+        gp = GenParams(max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
+                       subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
+        N, P = emb.shape[0], emb.shape[1]
+        gp.check_rows(N)
+        n_real = mask.sum(-1).tolist()
+        reqs = [(emb[i, P - int(n_real[i]):], trail[i], None if frame_caps is None else frame_caps[i])
+                for i in range(N)]
+        B = max(1, min(int(max_batch), N))
+        first, every = max(1, int(first_chunk_frames)), max(1, int(chunk_frames))
+        caps = sorted({first, every})  # feed capacities (one captured codec graph each)
+        dev = self.device
+        rs = dec.row_stream(B, RX + RC, caps[-1])
+        rows_ix = torch.arange(B, device=dev)[:, None]
+        req = [-1] * B        # request in each slot, as the codec has seen it
+        discard = [0] * B     # samples of the slot's decode still to drop (a restarted chunk's context)
+        cum = [0] * B         # samples handed out for the slot's request
+        nz = [0] * B          # nonzero cb0 among the request's final frames
+        try:
+            for s, report in self.engine.serve_iter(reqs, pad, gp, slots=B, use_graph=use_graph, every=every,
+                                                    first=first, philox_ids=philox_ids):
+                # per slot: the frames to feed, and the positions in that list at which the row (re)starts
+                todo, marks, ended = [[] for _ in range(B)], [{} for _ in range(B)], [False] * B
+                for b, r in enumerate(report):
+                    if r is None:
+                        continue
+                    i, lo, f, ended[b], nzb = r
+                    if req[b] != i:
+                        req[b], discard[b], cum[b], nz[b] = i, 0, 0, 0
+                    nz[b] += nzb
+                    for t in range(lo, f):
+                        if t % RC == 0:  # frame t opens a reference chunk: begin, after chunk 0 on the 25 context frames
+                            ctx = RX if t else 0
+                            marks[b][len(todo[b])] = ctx * up
+                            todo[b] += range(t - ctx, t)
+                        todo[b].append(t)
+                    if ended[b] and not todo[b]:  # nothing new: the request's audio was complete already
+                        yield i, torch.zeros(0, device=dev), True
+                at = [0] * B
+                while any(at[b] < len(todo[b]) for b in range(B)):
+                    nrow, begin = [0] * B, [0] * B
+                    for b in range(B):
+                        hi = min(len(todo[b]), at[b] + caps[-1])
+                        nxt = [m for m in marks[b] if at[b] < m < hi]  # a restart opens a feed of its own
+                        nrow[b] = (min(nxt) if nxt else hi) - at[b]
+                        begin[b] = int(nrow[b] > 0 and at[b] in marks[b])
+                    n = next(c for c in caps if c >= max(nrow))
+                    ix = torch.tensor([todo[b][at[b]:at[b] + nrow[b]] + [0] * (n - nrow[b]) for b in range(B)],
+                                      dtype=torch.long).pin_memory().to(dev, non_blocking=True)
+                    pcm = rs.feed(s.codes[rows_ix, ix], nrow, begin)
+                    for b in range(B):
+                        if not nrow[b]:
+                            continue
+                        if begin[b]:
+                            discard[b] = marks[b][at[b]]
+                        at[b] += nrow[b]
+                        lo_s, hi_s = 555 if begin[b] else 0, up * nrow[b]
+                        d = min(discard[b], hi_s - lo_s)
+                        discard[b] -= d
+                        lo_s += d
+                        last = ended[b] and at[b] == len(todo[b])
+                        if ended[b]:  # the reference's length rule: 1920 x #nonzero cb0 of the whole request
+                            hi_s = min(hi_s, lo_s + max(up * nz[b] - cum[b], 0))
+                        if hi_s > lo_s or last:
+                            cum[b] += hi_s - lo_s
+                            yield req[b], pcm[b, lo_s:hi_s].clone(), last
+        finally:
+            rs.close()
 
     @staticmethod
     def _stream_window(codes, pre, R, end, lo, hi):

@@ -10,6 +10,7 @@ Per-request state lives in a `Session` object, never on the module (fixes the re
 """
 from __future__ import annotations
 
+import time
 from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Dict, List, Optional
@@ -920,19 +921,7 @@ class TalkerEngine:
         H, dev = self.talker.H, self.dev
         try:
             with K.use_workspace(s.ws):
-                # the first B requests start together: one left-padded batched prefill (as generate() does)
-                Pb = max(int(r[0].shape[0]) for r in requests[:B])
-                Tb = max(int(r[1].shape[0]) for r in requests[:B])
-                emb = torch.zeros(B, Pb, H, dtype=torch.float32, device=dev)
-                mask = torch.zeros(B, Pb, dtype=torch.long, device=dev)
-                trail = tts_pad.reshape(1, 1, H).float().to(dev).repeat(B, Tb, 1)
-                for b in range(B):
-                    e, tr = requests[b][0], requests[b][1]
-                    emb[b, Pb - e.shape[0]:] = e
-                    mask[b, Pb - e.shape[0]:] = 1
-                    trail[b, :tr.shape[0]] = tr
-                self._prefill(s, emb, mask, trail, tts_pad, seed, pids[:B], gp=gp)
-                s.hiddens[:, 0].copy_(s.past_hidden)
+                Pb = self._serve_start(s, requests, B, tts_pad, seed, pids, gp)
                 queue = list(range(B, n))
                 slot_req = list(range(B))
                 epoch = [0] * B
@@ -1002,6 +991,106 @@ class TalkerEngine:
                         hit = (hc[:F + 1, 0] == eos).nonzero()
                         F = int(hit[0]) if hit.numel() else F
                         yield i, hc[:F].long(), hh[:F].clone()
+                check_handoffs([s])
+                self.serve_stats = {"frames": frame, "slots": B, "requests": n}
+        finally:
+            self.release([s])
+
+    def _serve_start(self, s: Session, requests, B, tts_pad, seed, pids, gp):
+        """The first B requests of a continuous-batching run start together: one left-padded batched prefill (as
+        generate() does).  Returns the padded prompt length."""
+        H, dev = self.talker.H, self.dev
+        Pb = max(int(r[0].shape[0]) for r in requests[:B])
+        Tb = max(int(r[1].shape[0]) for r in requests[:B])
+        emb = torch.zeros(B, Pb, H, dtype=torch.float32, device=dev)
+        mask = torch.zeros(B, Pb, dtype=torch.long, device=dev)
+        trail = tts_pad.reshape(1, 1, H).float().to(dev).repeat(B, Tb, 1)
+        for b in range(B):
+            e, tr = requests[b][0], requests[b][1]
+            emb[b, Pb - e.shape[0]:] = e
+            mask[b, Pb - e.shape[0]:] = 1
+            trail[b, :tr.shape[0]] = tr
+        self._prefill(s, emb, mask, trail, tts_pad, seed, pids[:B], gp=gp)
+        s.hiddens[:, 0].copy_(s.past_hidden)
+        return Pb
+
+    def serve_iter(self, requests, tts_pad, gp: GenParams, slots: int = 8, use_graph: bool = True, every: int = 8,
+                   first: int = 1, philox_ids=None):
+        """serve() observed as it runs (TTSModel.serve_stream): the same session, prefills, frame graph, refills and
+        Philox streams, so request i gets the codes serve() gives it, but progress is reported every `every` frame
+        replays, and `first` replays after a slot's refill, instead of whole requests at their end.
+
+        Yields (session, report), report = one (i, lo, f, ended, nz) per busy slot b (None for an idle one): frames
+        [lo, f) of request i, rows session.codes[b, lo:f], have become final since the slot's last report, nz of them
+        with a nonzero cb0 (the reference's length rule counts those); `ended` when the request is over (EOS, or its
+        frame limit) and F_i = f.  The consumer reads session.codes in stream
+        order before it resumes the generator, which then refills the ended slots.  One host sync per report (the
+        cb0 columns of the new frames and the hand-off flag word, copied together): a hand-off give-up raises
+        HandoffError before the frames it covers are reported."""
+        n = len(requests)
+        pids = list(range(n)) if philox_ids is None else [int(x) for x in philox_ids]
+        gp.check_rows(n)
+        if n == 0:
+            return
+        B = max(1, min(slots, n))
+        max_frames = max(gp.max_new_tokens - 1, 1)
+        P = max(int(r[0].shape[0]) for r in requests)
+        cap_i = [min(max_frames, int(r[2])) if len(r) > 2 and r[2] is not None else max_frames for r in requests]
+        seed = gp.resolve_seed()
+        eos = self.tc["codec_eos_token_id"]
+        s = self.session(B, P, max_frames, gp)
+        try:
+            with K.use_workspace(s.ws):
+                # request -> host time at which its prefill was queued (tools/serve_bench.py --stream)
+                self.serve_queued = dict.fromkeys(range(B), time.perf_counter())
+                Pb = self._serve_start(s, requests, B, tts_pad, seed, pids, gp)
+                queue = list(range(B, n))
+                slot_req = list(range(B))
+                start = [0] * B      # host frame count when the slot's request started
+                slot_p = [Pb] * B    # prompt length of each slot's request
+                seen = [0] * B       # frames of the slot's request already reported
+                fresh = [True] * B   # the slot's request has not been reported yet
+                frame, last_report = 0, 0
+                while any(r >= 0 for r in slot_req):
+                    busy = [b for b in range(B) if slot_req[b] >= 0]
+                    keys = max(slot_p[b] + frame - start[b] + 1 for b in busy)
+                    self._run_frame(s, min(keys, s.Lmax), use_graph)
+                    frame += 1
+                    if not (frame - last_report >= every or any(fresh[b] and frame - start[b] >= first for b in busy)):
+                        continue
+                    last_report = frame
+                    # frames [0, k_b) of slot b are final and column k_b holds its next cb0 (EOS of an ending request)
+                    k = [min(frame - start[b], cap_i[slot_req[b]]) if slot_req[b] >= 0 else 0 for b in range(B)]
+                    c0 = torch.empty(B, max(k) + 1, dtype=torch.int32, pin_memory=True)
+                    c0.copy_(s.codes[:, :max(k) + 1, 0], non_blocking=True)
+                    fw = _flag_word(s)
+                    hf = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+                    if fw is not None:
+                        hf.copy_(fw, non_blocking=True)
+                    torch.cuda.current_stream(self.dev).synchronize()
+                    if int(hf[0]) != 0:  # session-wide and sticky: every request in flight is suspect
+                        _clear_flags(s)
+                        raise HandoffError({r for r in slot_req if r >= 0}, queue)
+                    report = [None] * B
+                    for b in busy:
+                        hit = (c0[b, seen[b]:k[b] + 1] == eos).nonzero()
+                        f = seen[b] + int(hit[0]) if hit.numel() else k[b]
+                        ended = bool(hit.numel()) or k[b] >= cap_i[slot_req[b]]
+                        report[b] = (slot_req[b], seen[b], f, ended, int((c0[b, seen[b]:f] != 0).sum()))
+                        seen[b], fresh[b] = f, False
+                    yield s, report
+                    for b in busy:
+                        if not report[b][3]:
+                            continue
+                        start[b], seen[b], fresh[b] = frame, 0, True
+                        slot_req[b] = queue.pop(0) if queue else -1
+                        if slot_req[b] >= 0:
+                            self.serve_queued[slot_req[b]] = time.perf_counter()
+                            slot_p[b] = int(requests[slot_req[b]][0].shape[0])
+                            self._prefill_slot(s, b, requests[slot_req[b]], pids[slot_req[b]],
+                                               gp.row_records(slot_req[b], seed) if gp.per_row else None)
+                        else:
+                            s.finished[b:b + 1].fill_(1)  # idle slot: emits EOS until the session ends
                 check_handoffs([s])
                 self.serve_stats = {"frames": frame, "slots": B, "requests": n}
         finally:

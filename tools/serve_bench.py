@@ -11,7 +11,11 @@ voice-design wrapper's default; sampling with the wrapper defaults).  Per reques
 
 Both include prompt assembly and the codec decode of every request.  Prints one JSON line per schedule.
 
-    python tools/serve_bench.py [--requests 8] [--slots 8] [--extra-slots 16,32]
+--stream adds a third schedule, TTSModel.serve_stream on the same list: the rows are refilled as in
+`serve`, and every request's audio leaves in chunks while it decodes.  Its line also gives, per request, the time
+from the moment its prefill was queued to its first chunk being complete on the host's side of the stream (p50, p90).
+
+    python tools/serve_bench.py [--requests 8] [--slots 8] [--extra-slots 16,32] [--stream]
 """
 from __future__ import annotations
 
@@ -51,6 +55,8 @@ def main():
     ap.add_argument("--slots", type=int, default=8)
     ap.add_argument("--extra-slots", default="")
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--stream", action="store_true", help="also run the list through serve_stream")
+    ap.add_argument("--chunk-frames", type=int, default=8)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from qwen_tts import Qwen3TTSModel
@@ -93,6 +99,37 @@ def main():
             codes[i] = c
         return codes
 
+    first_ms = []
+
+    def stream(slots, seed):
+        """serve_stream: returns the samples received per request; first-chunk latencies go to first_ms"""
+        got, lat = [0] * len(reqs), {}
+        it = m.serve_stream(input_ids=[r[0] for r in reqs], instruct_ids=[r[1] for r in reqs],
+                            languages=["english"] * len(reqs), non_streaming_mode=True, max_new_tokens=max(F) + 1,
+                            seed=seed, frame_caps=F, max_batch=slots, first_chunk_frames=1,
+                            chunk_frames=a.chunk_frames, **gen)
+        for i, pcm, last in it:
+            if i not in lat:  # the chunk is usable once the stream has produced it
+                torch.cuda.current_stream().synchronize()
+                lat[i] = (time.perf_counter() - eng.serve_queued[i]) * 1e3
+            got[i] += pcm.numel()
+        first_ms[:] = [lat[i] for i in range(len(reqs))]
+        return got
+
+    def run_stream(slots):
+        stream(slots, 1)  # warmup (graph captures, sessions, codec slot)
+        ts, lats = [], []
+        for r in range(a.reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = stream(slots, 10 + r)
+            torch.cuda.synchronize()
+            ts.append(time.perf_counter() - t0)
+            lats += first_ms
+            # every frame's 1920 samples but each reference chunk's last 555 (fewer only where a cb0 is 0)
+            assert all(0 < g <= 1920 * f - 555 * -(-f // 300) for g, f in zip(got, F)), got
+        return ts, lats
+
     def run(fn, slots):
         fn(slots, 1)  # warmup (graph capture, sessions)
         ts = []
@@ -104,21 +141,39 @@ def main():
             wavs, sr = m.speech_tokenizer.decode([{"audio_codes": c} for c in codes])
             torch.cuda.synchronize()
             ts.append(time.perf_counter() - t0)
-        return float(np.median(ts))
+        return ts
 
     slot_list = [a.slots] + [int(x) for x in a.extra_slots.split(",") if x]
     for name, fn in (("padded", padded), ("serve", serve)):
         for slots in slot_list:
             if name == "padded" and slots != a.slots:
                 continue
-            dt = run(fn, slots)
+            ts = run(fn, slots)
+            dt = float(np.median(ts))
             st = getattr(eng, "serve_stats", {}) if name == "serve" else {}
             print(json.dumps({"schedule": name, "slots": slots, "requests": a.requests, "frames": F,
                               "frames_replayed": st.get("frames"), "frames_min": -(-sum(F) // slots),
                               "audio_s": round(audio_s, 2), "wall_s": round(dt, 4),
                               "audio_s_per_s": round(audio_s / dt, 2),
+                              "audio_s_per_s_runs": [round(audio_s / t, 2) for t in ts],
                               "workload": f"{a.preset} configs[3] shard, text U[40,300], instruct U[10,60], "
                                           "F U[64,320], sampling, ignore_eos + per-request cap, + codec decode"}),
+                  flush=True)
+    if a.stream:
+        for slots in slot_list:
+            ts, lats = run_stream(slots)
+            dt = float(np.median(ts))
+            st = getattr(eng, "serve_stats", {})
+            print(json.dumps({"schedule": "serve_stream", "slots": slots, "requests": a.requests,
+                              "chunk_frames": a.chunk_frames, "frames_replayed": st.get("frames"),
+                              "frames_min": -(-sum(F) // slots), "audio_s": round(audio_s, 2),
+                              "wall_s": round(dt, 4), "audio_s_per_s": round(audio_s / dt, 2),
+                              "audio_s_per_s_runs": [round(audio_s / t, 2) for t in ts],
+                              "first_chunk_p50_ms": round(float(np.percentile(lats, 50)), 2),
+                              "first_chunk_p90_ms": round(float(np.percentile(lats, 90)), 2),
+                              "first_chunk_first_batch_p50_ms": round(float(np.percentile(
+                                  [x for r in range(a.reps) for x in lats[r * len(reqs):r * len(reqs) + slots]], 50)), 2),
+                              "workload": "as above, audio streamed per request (first chunk 1 frame)"}),
                   flush=True)
 
 
