@@ -127,7 +127,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_talker_tail", "qt_talker_tail_ws_bytes", "qt_talker_tail_stamp_bytes", "qt_talker_tail_dbg_bytes",
            "qt_talker_tail_supported",
            "qt_sample", "qt_sample_row_bytes", "qt_sample_args_bytes", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
-           "qt_stream_window", "qt_stream_rows",
+           "qt_stream_window", "qt_stream_rows", "qt_trail_append",
            "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
@@ -178,6 +178,7 @@ def load_library(path: str = LIB_PATH):
         "qt_frame_embed": [P, P, c_int, c_int, c_int, c_int, c_int, P, c_ll, P, c_int, P, c_int, P, P, P, c_int, P],
         "qt_advance": [P, c_int, P],
         "qt_advance_rows": [P, c_int, c_int, c_int, P],
+        "qt_trail_append": [P, P, P, c_int, c_int, c_int, c_int, P],
         "qt_stream_window": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
         "qt_stream_rows": [P, P, c_int, c_int, P, P, P],
         "qt_rvq_gather": [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P],

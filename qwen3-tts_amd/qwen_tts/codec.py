@@ -466,7 +466,7 @@ class CodecStream:
         side = torch.cuda.Stream(device=self.dec.dev)
         side.wait_stream(torch.cuda.current_stream(self.dec.dev))
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side):
+        with torch.cuda.stream(side), K.capturing():
             with torch.cuda.graph(g, stream=side):
                 out = self._compute(cin, n, first)
         torch.cuda.current_stream(self.dec.dev).wait_stream(side)
@@ -689,7 +689,7 @@ class RowCodecStream:
         side = torch.cuda.Stream(device=self.dec.dev)
         side.wait_stream(torch.cuda.current_stream(self.dec.dev))
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side):
+        with torch.cuda.stream(side), K.capturing():
             with torch.cuda.graph(g, stream=side):
                 out = self._compute(cin, n)
         torch.cuda.current_stream(self.dec.dev).wait_stream(side)

@@ -392,8 +392,8 @@ class Qwen3TTSModel:
         return self._decode(codes)
 
     @torch.no_grad()
-    def stream(self, text, speaker=None, language=None, instruct=None, non_streaming_mode=True,
-               first_chunk_frames=1, chunk_frames=48, left_context=None, max_batch=None, **kwargs):
+    def stream(self, text, speaker=None, language=None, instruct=None, non_streaming_mode=None,
+               first_chunk_frames=1, chunk_frames=48, left_context=None, max_batch=None, text_feed=None, **kwargs):
         """New surface (no reference counterpart): streaming custom-voice generation.
         Yields (utterance index, pcm chunk np.float32, sample rate, is_last) while the batch decodes: the first
         chunk arrives after prefill + `first_chunk_frames` decode frames (1 frame: 1365 samples = 57 ms of audio,
@@ -403,15 +403,37 @@ class Qwen3TTSModel:
         (a stateful incremental codec decode; codes are identical -- see TTSModel.stream for the chunk rule and the
         stateless `left_context` form).  max_batch: with more utterances than max_batch, they stream through
         max_batch continuously batched rows instead (TTSModel.serve_stream): a row is refilled with the next
-        utterance as soon as its own ends, and every utterance has a first chunk of its own."""
+        utterance as soon as its own ends, and every utterance has a first chunk of its own.
+
+        text_feed (a qwen_tts.TextFeed, one row per utterance): the text arrives while the audio is
+        generated (make it with self.text_feed(rows, timeout), so that push_text works before the first next()).
+        `text` then holds each utterance's first piece (at least one token); later pieces come through
+        text_feed.push_text(piece, row) -- or push(ids, row) -- from any thread, and text_feed.close(row) ends an
+        utterance's text.  Each piece is tokenized on its own, and piece-wise BPE is not the whole sentence's BPE
+        (cut at word boundaries); what is guaranteed is stated on ids: after close, an utterance is decoded exactly
+        as the whole id sequence would be in streaming-text mode (non_streaming_mode=False, the only mode here).
+        non_streaming_mode defaults to True as in generate_custom_voice(), and to False with a text_feed."""
+        if non_streaming_mode is None:
+            non_streaming_mode = text_feed is None
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
+        if text_feed is not None:  # heads: role ids + the first piece, no template suffix
+            input_ids = self._tokenize_texts([f"<|im_start|>assistant\n{t}" for t in self._ensure_list(text)])
+            text_feed.processor = self.processor
         sr = self.model.speech_tokenizer.get_output_sample_rate()
         for i, pcm, last in self.model.stream(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                               speakers=speakers, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
-                                              left_context=left_context, max_batch=max_batch,
+                                              left_context=left_context, max_batch=max_batch, text_feed=text_feed,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, pcm.to(torch.float32).cpu().numpy(), sr, last
+
+    def text_feed(self, rows: int = 1, timeout: float = 30.0):
+        """A qwen_tts.TextFeed for stream(text_feed=...) whose push_text tokenizes with this model's processor (usable
+        at once: stream() is a generator and binds the processor of a plain TextFeed only at its first next())."""
+        from ..feed import TextFeed
+        feed = TextFeed(rows=rows, timeout=timeout)
+        feed.processor = self.processor
+        return feed
 
     def get_supported_speakers(self) -> Optional[List[str]]:
         s = self._supported_speakers_set()

@@ -5,7 +5,9 @@ the current stream, so the calls are capturable into HIP graphs.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 import threading
 from dataclasses import dataclass
 from typing import Optional
@@ -164,6 +166,21 @@ class use_workspace:
 
     def __exit__(self, *exc):
         _active_stack().pop()
+
+
+@contextlib.contextmanager
+def capturing():
+    """Around a stream capture: Python's cycle collector is paused.  A CUDAGraph that the collector frees while a
+    stream captures (a dropped session's graphs, say, kept alive until then by a reference cycle) destroys its HIP
+    graph, which a global-mode capture does not permit on this thread: torch raises from the destructor and the
+    process aborts.  torch.cuda.graph() itself no longer collects before it begins."""
+    on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if on:
+            gc.enable()
 
 
 def active_workspace(device):
@@ -466,6 +483,13 @@ def advance(counters, n):
 def advance_rows(counters, B, nfields, cap):
     """Per-row counters [nfields][B] (field 0 = frame index): rows below cap advance every field by one."""
     check(_hip.lib().qt_advance_rows(ptr(counters), B, nfields, cap, stream()), "qt_advance_rows")
+
+
+def trail_append(rows, slots, trailing, n):
+    """trailing[row_j][pos_j] = rows[j] for the n entries {row_j, pos_j} of slots (int32 [n][2]); entries outside
+    trailing's [B][T] are skipped.  rows fp32 [n][H], trailing fp32 [B][T][H]."""
+    B, T, H = trailing.shape
+    check(_hip.lib().qt_trail_append(ptr(rows), ptr(slots), ptr(trailing), B, T, H, n, stream()), "qt_trail_append")
 
 
 def stream_window(hist, x, xin, B, H, n, C, rows_per_frame, head, rows):

@@ -113,13 +113,19 @@ class TTSModel:
         return text + codec, pad_e
 
     def build_prompts(self, input_ids, languages, speakers=None, instruct_ids=None, non_streaming_mode=False,
-                      voice_clone_prompt=None, ref_ids=None):
+                      voice_clone_prompt=None, ref_ids=None, open_text=False):
         """(embeds [B,P,H] fp32, mask [B,P], trailing [B,T,H], tts_pad [1,1,H]) -- M:2068-2269.
+        open_text (streaming-text input; not in the reference): the ids are a request's head -- the three
+        role ids and the text known so far, no template suffix -- so every id after the fourth goes to the trailing
+        rows and no end-of-text position follows them (the text is not complete; stream(text_feed=...) appends it).
         Two passes: the rows' text-id and codec-id runs are collected on the host first, then projected in one
         text_projection and one codec-embedding gather for the whole batch (one host->device copy each instead of
         a few per row: the per-row calls were host-bound, ~3.3 ms at B=8), and each row is assembled from slices."""
         e, t, cfg = self.engine, self.tc, self.config
         B = len(input_ids)
+        if open_text and non_streaming_mode:
+            raise ValueError("open_text prompts are streaming-text prompts: non_streaming_mode=True puts the whole "
+                             "text into the prefill")
         runs = _Runs()
         spk_embeds = None
         if voice_clone_prompt is not None:
@@ -175,11 +181,11 @@ class TTSModel:
                     pl["txt_pad"] = runs.codec([t["codec_pad_id"]] * (n + 1))
                     pl["end_bos"] = runs.codec([t["codec_bos_id"]])
                 else:
-                    pl["trail"] = runs.text(ids[4:-5])
+                    pl["trail"] = runs.text(ids[4:] if open_text else ids[4:-5])
             plans.append(pl)
         runs.run(e)
         if not any(pl["icl"] for pl in plans):
-            return self._assemble_indexed(runs, plans, h_ins, h_special, non_streaming_mode)
+            return self._assemble_indexed(runs, plans, h_ins, h_special, non_streaming_mode, open_text)
         special = runs.get(h_special)[0]
         bos_e, eos_e, pad_e = special[0].view(1, 1, -1), special[1].view(1, 1, -1), special[2].view(1, 1, -1)
         per: List[list] = [[] if h_ins[i] is None else [runs.get(h_ins[i])] for i in range(B)]
@@ -206,7 +212,7 @@ class TTSModel:
                     emb = torch.cat([emb, txt, pad_e + runs.get(pl["end_bos"])], 1)
                     trail = pad_e
                 else:
-                    trail = torch.cat([runs.get(pl["trail"]), eos_e], 1)
+                    trail = torch.cat([runs.get(pl["trail"]), pad_e if open_text else eos_e], 1)
             per[i].append(emb)
             trailing.append(trail)
         seqs = [torch.cat(p, 1)[0] for p in per]
@@ -223,7 +229,7 @@ class TTSModel:
             trail[i, :tr.shape[1]] = tr[0]
         return embeds, mask, trail, pad_e
 
-    def _assemble_indexed(self, runs, plans, h_ins, h_special, non_streaming_mode):
+    def _assemble_indexed(self, runs, plans, h_ins, h_special, non_streaming_mode, open_text=False):
         """build_prompts' assembly for non-ICL rows as one gather: every prompt / trailing position is the sum of at
         most two rows of [text projections; codec embeddings; x-vectors; zero row], so the host writes a [positions,
         2] index table and three GPU ops build the whole batch (the per-row slicing / cat / add chain was ~120
@@ -262,7 +268,9 @@ class TTSModel:
             else:
                 if pl["first"][2]:  # (a prompt without a first text token has no such position, as in the chain)
                     pos.append((t(pl["first"]), ci[-1]))
-                trails.append([(t(pl["trail"], j), Z) for j in range(pl["trail"][2])] + [(eos, Z)])
+                # (open text: no end-of-text position yet; a pad one keeps the row non-empty)
+                trails.append([(t(pl["trail"], j), Z) for j in range(pl["trail"][2])] +
+                              [(pad if open_text else eos, Z)])
             seqs.append(pos)
         P, T = max(len(s) for s in seqs), max(len(tr) for tr in trails)
         idx = [[(Z, Z)] * (P - len(s)) + s for s in seqs] + [tr + [(pad, Z)] * (T - len(tr)) for tr in trails]
@@ -342,7 +350,8 @@ class TTSModel:
                speakers=None, non_streaming_mode=False, max_new_tokens=4096, do_sample=True, top_k=50, top_p=1.0,
                temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
-               first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None, **kwargs):
+               first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None,
+               text_feed=None, **kwargs):
         """Streaming generation (the reference has none): yields (row, pcm, last) as frames finish.
 
         Per row the chunks concatenate to the one-shot generate() + decode() PCM (Z:259-365): the reference
@@ -358,7 +367,25 @@ class TTSModel:
         generate().  pcm is a 1-D fp32 device tensor of 24 kHz samples.
 
         max_batch: with more requests than max_batch, stream them by continuous batching through max_batch batch
-        rows (serve_stream(): a row is refilled as soon as its request ends; chunk_frames then defaults to 8)."""
+        rows (serve_stream(): a row is refilled as soon as its request ends; chunk_frames then defaults to 8).
+
+        text_feed: a qwen_tts.TextFeed with one row per request -- the text arrives while the audio is
+        generated.  input_ids[b] is then the request's head: the three role ids and at least one text id, no template
+        suffix.  The prefill holds the first text id; later ones, from the head or pushed, are read one per frame, and
+        a frame is queued only when every row that is neither closed nor finished has its token.  With
+        first_chunk_frames=1 the first packet needs the first text id alone.  After feed.close(b), row b has decoded
+        exactly what a whole-text call with role + text + suffix ids decodes in streaming-text mode.  When the text
+        runs out, all audio generated so far is yielded, then the loop waits up to feed.timeout seconds and raises
+        TextFeedTimeout.  Only the thread running this generator issues GPU work; push / close may come from any."""
+        if text_feed is not None:
+            yield from self._stream_fed(text_feed, input_ids, instruct_ids, voice_clone_prompt, languages, speakers,
+                                        non_streaming_mode, left_context, max_batch, first_chunk_frames, chunk_frames,
+                                        use_graph,
+                                        GenParams(max_new_tokens, do_sample, top_k, top_p, temperature,
+                                                  subtalker_dosample, subtalker_top_k, subtalker_top_p,
+                                                  subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos,
+                                                  seed))
+            return
         if max_batch is not None and input_ids is not None and len(input_ids) > int(max_batch):
             if left_context is not None:
                 raise NotImplementedError("stream(left_context=...) with max_batch: use the default stateful stream")
@@ -458,6 +485,40 @@ class TTSModel:
                         yield b, torch.zeros(0, device=codes.device), True
             if all(done):
                 break
+
+    def _stream_fed(self, feed, heads, instruct_ids, voice_clone_prompt, languages, speakers, non_streaming_mode,
+                    left_context, max_batch, first_chunk_frames, chunk_frames, use_graph, gp):
+        """stream(text_feed=feed): the combinations it does not serve are refused before anything is allocated."""
+        from .feed import TextFeed
+        from .talker import TextGate
+        refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
+        if refs is not None and any(r is not None for r in refs):
+            raise NotImplementedError("stream(text_feed=...) with voice-clone reference codes (ICL): the reference "
+                                      "text and codes take the text's place in the prefill; use x-vector-only prompts")
+        if max_batch is not None:
+            raise NotImplementedError("stream(text_feed=...) with max_batch: continuous batching takes whole texts")
+        if left_context is not None:
+            raise NotImplementedError("stream(text_feed=...) with left_context: use the default stateful stream")
+        if non_streaming_mode:
+            raise ValueError("stream(text_feed=...) needs non_streaming_mode=False: non-streaming mode puts the whole "
+                             "text into the prefill")
+        if not isinstance(feed, TextFeed):
+            raise ValueError(f"text_feed must be a qwen_tts.TextFeed, got {type(feed).__name__}")
+        heads = [torch.as_tensor(h).reshape(-1).tolist() for h in heads]
+        B = len(heads)
+        if feed.rows != B:
+            raise ValueError(f"text_feed has {feed.rows} rows for {B} requests")
+        for b, h in enumerate(heads):
+            if len(h) < 4:
+                raise ValueError(f"request {b}: a head is the three role ids plus at least one text id, got "
+                                 f"{len(h)} ids")
+        emb, mask, trail, pad = self.build_prompts(heads, languages, speakers, instruct_ids, False,
+                                                   voice_clone_prompt, None, open_text=True)
+        gp.check_rows(B)
+        gate = TextGate(feed, [len(h) - 4 for h in heads], self.config["tts_eos_token_id"])
+        yield from self._stream_stateful(self.speech_tokenizer.model, emb, mask, trail, pad, gp, B,
+                                         self.engine.tc["codec_eos_token_id"], first_chunk_frames, chunk_frames,
+                                         use_graph, gate=gate)
 
     @torch.no_grad()
     def serve_stream(self, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None, languages=None,
@@ -596,7 +657,7 @@ class TTSModel:
         return pre, side, cs, fed
 
     def _stream_stateful(self, dec, emb, mask, trail, pad, gp, B, eos, first_chunk_frames, chunk_frames, use_graph,
-                         prefix=None, started=None):
+                         prefix=None, started=None, gate=None):
         """stream() on the incremental codec: every final frame is fed once to the decoder of its reference chunk
         and every sample computable from the frames fed so far is emitted -- 1920 n - 555 samples of a chunk after
         its n frames, i.e. no lookahead frame is waited for (the 555 samples that need it follow with the next
@@ -637,7 +698,8 @@ class TTSModel:
         # a one-frame first chunk is handed over as soon as frame 0's codes exist: its codec window is queued before the
         # talker step that starts frame 1 (the first packet does not wait for it)
         it = self.engine.decode_iter(emb, mask, trail, pad, gp, use_graph=use_graph, every=chunk_frames,
-                                     first=first_chunk_frames, grow=True, early_first=first_chunk_frames == 1)
+                                     first=first_chunk_frames, grow=True, early_first=first_chunk_frames == 1,
+                                     gate=gate)
         try:
             for sessions, frames, final in it:
                 if side is not None:

@@ -11,7 +11,7 @@ Per-request state lives in a `Session` object, never on the module (fixes the re
 from __future__ import annotations
 
 import time
-from collections import OrderedDict
+from collections import OrderedDict, deque
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
@@ -493,7 +493,60 @@ class Session:
         self.slot_prefill = OrderedDict()  # P -> static single-request prefill buffers (serve() refills); LRU
         self.busy = False  # held by a live decode_iter (a suspended stream() generator included)
         self.watch = None  # HandoffWatch armed at the last yield of decode_iter
+        self.txt = None    # text-append buffers + captured append graph (TalkerEngine.append_text), built on first use
         self.cp = CPLane(self, eng, 0, B, self.ws)
+
+
+class TextGate:
+    """The host's account of a streamed request's trailing text: which positions of Session.trailing are
+    written, per row, and therefore which frame replays may be queued.  The host is the authority: the frame kernels
+    read whatever the buffer holds.  Used by the thread that runs the generator only; other threads touch the feed."""
+
+    # Tokens are projected a little ahead of the frames, not all at once: a backlog of 8 x 200 tokens is 100 appends,
+    # which in front of the first replay cost 2.1 ms of a 6.2 ms first packet.  When a row's next unwritten position
+    # is fewer than LOW frames ahead of the replay about to be queued, every row is written up to AHEAD frames ahead.
+    LOW, AHEAD = 8, 24
+
+    def __init__(self, feed, n0, eos_id: int):
+        self.feed, self.eos_id = feed, int(eos_id)
+        self.n = [int(x) for x in n0]          # trailing tokens present so far (in the head, or pushed)
+        self.todo = [deque() for _ in self.n]  # (pos, id) received, not yet written to the trailing buffer
+        self.closed = [False] * len(self.n)    # the row's end-of-text position is written
+        self.finished = [False] * len(self.n)  # the row is known to have reached its end-of-speech token
+        self.eng = self.s = None
+
+    def bind(self, eng, s, max_frames: int, use_graph: bool):
+        self.eng, self.s, self.cap, self.use_graph = eng, s, int(max_frames), use_graph
+
+    def poll(self, f: int = 0):
+        """Drain the feed without blocking; queue the projections of the tokens that replay f and the next ones read
+        into the trailing buffer.  Positions at or past the frame cap are dropped: no frame reads them."""
+        pieces, closed = self.feed.drain()
+        vocab = self.eng.text_emb.shape[0]
+        for b, ids in enumerate(pieces):
+            for t in ids:
+                if not 0 <= t < vocab:  # the gather would read outside the embedding table
+                    raise ValueError(f"text id {t} pushed for row {b} is outside the text vocabulary ({vocab})")
+                if self.n[b] < self.cap:
+                    self.todo[b].append((self.n[b], t))
+                self.n[b] += 1
+        for b in closed:
+            if self.n[b] < self.cap:
+                self.todo[b].append((self.n[b], self.eos_id))
+            self.closed[b] = True
+        if any(q and q[0][0] < f + self.LOW for q in self.todo):
+            items = []
+            for b, q in enumerate(self.todo):
+                while q and q[0][0] < f + self.AHEAD:
+                    items.append((b,) + q.popleft())
+            self.eng.append_text(self.s, items, self.use_graph)
+
+    def row_ready(self, b: int, f: int) -> bool:
+        return self.closed[b] or self.finished[b] or self.n[b] > f
+
+    def ready(self, f: int) -> bool:
+        """Frame replay f (it reads trailing[b, f]) may be queued."""
+        return all(self.row_ready(b, f) for b in range(len(self.n)))
 
 
 class TalkerEngine:
@@ -632,6 +685,8 @@ class TalkerEngine:
     def release(sessions):
         for s in sessions:
             s.busy = False
+            s.watch = None  # (it refers back to the session: a cycle would keep a dropped session, its K/V cache and
+            #                 its graphs, alive until the cycle collector runs -- possibly inside a later capture)
 
     def all_sessions(self) -> List[Session]:
         return [s for ss in self._sessions.values() for s in ss]
@@ -787,7 +842,8 @@ class TalkerEngine:
             self.release([s])
 
     def decode_iter(self, embeds, mask, trailing, tts_pad, gp: GenParams, use_graph: bool = True, on_frames=None,
-                    every: int = 0, first: int = 0, grow: bool = False, philox_ids=None, early_first: bool = False):
+                    every: int = 0, first: int = 0, grow: bool = False, philox_ids=None, early_first: bool = False,
+                    gate: "Optional[TextGate]" = None):
         """Prefill + frame loop as a generator: yields (sessions, frames_done, final) after `first` frames, then
         every `every` frames (0: only at the end; grow=True: intervals double from first - 1 up to `every`), and once
         at the end with final=True.  `sessions` is a one-element list (the batch's session); codes[:, :frames_done]
@@ -795,7 +851,8 @@ class TalkerEngine:
         that just finished).  early_first (with first == 1): the first yield comes as soon as frame 0's codes are
         complete -- after its code predictor, before the talker step that starts frame 1 (which is queued after the
         caller's work, e.g. the first codec window); at that yield codes[:, 1, 0] is not written yet (EOS cannot occur
-        there anyway: it is masked below min_new_tokens)."""
+        there anyway: it is masked below min_new_tokens).  gate (streaming-text input): a TextGate asked
+        before every frame replay whether the text position that replay reads has arrived (_frames_gated)."""
         B, P, H = embeds.shape
         gp.check_rows(B)
         max_frames = max(gp.max_new_tokens - 1, 0)
@@ -807,11 +864,19 @@ class TalkerEngine:
             sessions.append(s)
             with K.use_workspace(s.ws):
                 self._prefill(s, embeds, mask, trailing, tts_pad, seed, philox_ids, gp=gp)
-            yield from self._frames(sessions, [main], max_frames, use_graph, on_frames, every, first, grow, early_first)
+            if gate is not None:
+                gate.bind(self, s, max_frames, use_graph)
+            yield from self._frames(sessions, [main], max_frames, use_graph, on_frames, every, first, grow, early_first,
+                                    gate)
         finally:
             self.release(sessions)
 
-    def _frames(self, sessions, streams, max_frames, use_graph, on_frames, every, first, grow=False, early_first=False):
+    def _frames(self, sessions, streams, max_frames, use_graph, on_frames, every, first, grow=False, early_first=False,
+                gate=None):
+        if gate is not None:  # streaming-text input: a loop of its own, so that this one stays as it is
+            yield from self._frames_gated(sessions[0], max_frames, use_graph, on_frames, every, first, grow,
+                                          early_first, gate)
+            return
         main = torch.cuda.current_stream(self.dev)
         frames = 0
         check_every = 8
@@ -868,6 +933,179 @@ class TalkerEngine:
             main.wait_stream(st)
         check_handoffs(sessions)
         yield sessions, frames, True
+
+    def _frames_gated(self, s: Session, max_frames, use_graph, on_frames, every, first, grow, early_first, gate):
+        """_frames for one session whose trailing text arrives while it decodes.  Frame replay f reads
+        trailing[b, f], so it is queued only once gate.ready(f): every row that is neither closed nor known finished
+        has a text token there.  The gate drains its feed (no blocking) before every replay.  A one-frame first chunk
+        needs no text at all: frame 0's codes come from the prefill and the code predictor (the early_first split);
+        only the talk half of replay 0 waits.  When no replay can be queued the loop, in this order, reports every
+        frame finished so far (whatever `every` says), synchronises and reads the rows' finished flags (all finished:
+        the stream ends normally, text closed or not), and waits for the feed up to its timeout, then raises
+        TextFeedTimeout.  Yields as _frames does."""
+        from .feed import TextFeedTimeout
+        sessions = [s]
+        frames = 0            # frames whose 16 codes are complete
+        reported = 0          # ... as of the last yield
+        talk_due = False      # frame 0 was issued as its code predictor alone: its talk half is still to come
+        flags_at = None       # (frames, talk_due) when the finished flags were last read on a starved loop
+        deadline = None       # end of the current wait for text (None: not starved)
+        check_every = 8
+        next_yield = first or every
+        interval = max(first - 1, 1)
+        s.hiddens[:, 0].copy_(s.past_hidden)
+        pending = []
+        watch = None
+
+        def report():
+            nonlocal watch
+            if watch is not None:
+                watch.check()
+            watch = s.watch = HandoffWatch(sessions)
+            return sessions, frames, False
+
+        while frames < max_frames:
+            gate.poll(0 if talk_due else frames)
+            if early_first and frames == 0 and not talk_due and next_yield == 1 and max_frames > 1:
+                self._run_frame(s, s.P + 1, use_graph, "cp")  # no text position is read
+                frames, talk_due = 1, True
+                if on_frames is not None:
+                    on_frames(s, frames)
+                reported = frames
+                yield report()
+                interval = min(every, 2 * interval) if grow else every
+                next_yield = frames + interval if every else 0
+                continue
+            f = 0 if talk_due else frames  # the replay to queue, i.e. the trailing position it reads
+            if not gate.ready(f):
+                if frames > reported:  # the listener gets all audio that exists
+                    reported = frames
+                    yield report()
+                    continue
+                if flags_at != (frames, talk_due):
+                    flags_at = (frames, talk_due)
+                    fin = s.finished.cpu()  # (synchronises)
+                    gate.finished = [bool(x) for x in fin.tolist()]
+                    if all(gate.finished):
+                        break
+                    continue
+                now = time.perf_counter()
+                if deadline is None:
+                    deadline = now + gate.feed.timeout
+                if now >= deadline or not gate.feed.wait(deadline - now):
+                    raise TextFeedTimeout(
+                        f"no text for frame {f} within {gate.feed.timeout} s: rows "
+                        f"{[b for b in range(s.B) if not gate.row_ready(b, f)]} are neither closed nor finished and "
+                        f"have {[gate.n[b] for b in range(s.B) if not gate.row_ready(b, f)]} trailing tokens")
+                continue
+            deadline = None
+            if talk_due:
+                self._run_frame(s, s.P + 1, use_graph, "talk")
+                talk_due = False
+                continue
+            self._run_frame(s, s.P + frames + 1, use_graph)
+            frames += 1
+            if on_frames is not None:
+                on_frames(s, frames)
+            if next_yield and frames == next_yield and frames < max_frames:
+                reported = frames
+                yield report()
+                interval = min(every, 2 * interval) if grow else every
+                next_yield = frames + interval if every else 0
+            if frames % check_every == 0 and frames < max_frames:
+                fl = torch.empty(1, dtype=torch.bool, pin_memory=True)
+                fl.copy_(s.finished.all().reshape(1), non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                pending.append((fl, ev))
+                done = False
+                while pending and pending[0][1].query():
+                    if bool(pending.pop(0)[0].item()):
+                        done = True
+                if done:
+                    break
+        check_handoffs(sessions)
+        yield sessions, frames, True
+
+    # ---------------------------------------------------------------- streaming-text input (DESIGN §15)
+    TXT_M = 16      # rows of every append launch: a fixed shape, so a token's projection does not depend on the piece
+    TXT_RING = 32   # staging slots of the pinned buffer (a slot is rewritten only after its copy has run)
+
+    def _txt_buffers(self, s: Session):
+        """The session's static append buffers: ids int32 [16] and slots int32 [16][2] (one device block, one copy),
+        fc1's output [16][fc1.N], the projected rows fp32 [16][H], one pinned staging buffer of TXT_RING slots."""
+        if s.txt is None:
+            dev, M = self.dev, self.TXT_M
+            inp = torch.zeros(3 * M, dtype=torch.int32, device=dev)
+            s.txt = {"in": inp, "ids": inp[:M], "slots": inp[M:].view(M, 2),
+                     "h": torch.zeros(M, self.fc1.N, dtype=torch.float32, device=dev),
+                     "out": torch.zeros(M, self.fc2.N, dtype=torch.float32, device=dev),
+                     "stage": torch.zeros(self.TXT_RING, 3 * M, dtype=torch.int32).pin_memory(),
+                     "stage_np": None,
+                     "events": [None] * self.TXT_RING, "turn": 0, "graph": None}
+            s.txt["stage_np"] = s.txt["stage"].numpy()  # the pinned slots, written without a tensor per append
+            self._check_append_routes(s)
+        return s.txt
+
+    def _check_append_routes(self, s: Session):
+        """The fixed 16-row launch must give each row the bits a 1-row launch gives it (the existing n <= 16 branch of
+        text_proj): both linears on the decode GEMV with the same K split over splits and waves at M = 1 and M = 16.
+        Anything else is an error, not a fall-back."""
+        tx, thd = s.txt, self.text_emb.shape[1]
+        for what, call in (("fc1", lambda m: K.gemm_route(self.text_emb, self.fc1, tx["h"], m, thd, self.fc1.N,
+                                                          a_dtype=self.text_emb.dtype, a_index=tx["ids"],
+                                                          act=_hip.ACT_SILU)),
+                           ("fc2", lambda m: K.gemm_route(tx["h"], self.fc2, tx["out"], m, self.fc1.N, self.fc2.N))):
+            with K.use_workspace(s.ws):
+                r1, r16 = call(1), call(self.TXT_M)
+            if not (r1.route == r16.route == _hip.ROUTE_GEMV and (r1.ks, r1.wpb) == (r16.ks, r16.wpb)):
+                raise NotImplementedError(
+                    f"text append: text_projection {what} does not take one decode-GEMV summation order at M = 1 and "
+                    f"M = {self.TXT_M} (route {r1.route}/{r16.route}, split-K {r1.ks}/{r16.ks}, waves {r1.wpb}/"
+                    f"{r16.wpb}); a token's projection would depend on how the text was cut")
+
+    def _append_compute(self, s: Session):
+        tx, M = s.txt, self.TXT_M
+        thd = self.text_emb.shape[1]
+        K.gemm(self.text_emb, self.fc1, tx["h"], M, thd, self.fc1.N, a_dtype=self.text_emb.dtype, a_index=tx["ids"],
+               act=_hip.ACT_SILU)
+        K.gemm(tx["h"], self.fc2, tx["out"], M, self.fc1.N, self.fc2.N)
+        K.trail_append(tx["out"], tx["slots"], s.trailing, M)
+
+    def append_text(self, s: Session, items, use_graph: bool = True):
+        """Write text tokens into the session's trailing buffer, in stream order: items = [(row, pos, id)], 16 per
+        launch.  Every launch has the same shape (16 rows; unused rows project token 0 and carry row = -1, which
+        qt_trail_append skips): one async copy of ids + slots, then gather + fc1 (SiLU) + fc2 + qt_trail_append,
+        captured once per session with use_graph and replayed.  (On a stream of their own, beside the frames, the
+        appends measured slower: frames/s -1.9 % at B = 1 and -1.8 % at B = 8 against -0.1 % / -0.3 % in stream order
+        -- profiles/text_feed_vs_stream.txt.)"""
+        tx, M = self._txt_buffers(s), self.TXT_M
+        for i0 in range(0, len(items), M):
+            part = items[i0:i0 + M]
+            k = tx["turn"] = (tx["turn"] + 1) % self.TXT_RING
+            if tx["events"][k] is not None:
+                tx["events"][k].synchronize()  # the copy that last read this slot has run
+            vals = [0] * M + [-1] * (2 * M)
+            for j, (row, pos, tid) in enumerate(part):
+                vals[j], vals[M + 2 * j], vals[M + 2 * j + 1] = int(tid), int(row), int(pos)
+            tx["stage_np"][k, :] = vals
+            tx["in"].copy_(tx["stage"][k], non_blocking=True)
+            ev = tx["events"][k] = torch.cuda.Event()
+            ev.record()
+            if not use_graph:
+                with K.use_workspace(s.ws):
+                    self._append_compute(s)
+                continue
+            if tx["graph"] is None:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.stream(side), K.use_workspace(s.ws), K.capturing():
+                    with torch.cuda.graph(g, stream=side):
+                        self._append_compute(s)
+                torch.cuda.current_stream().wait_stream(side)
+                tx["graph"] = g
+            tx["graph"].replay()
 
     def collect(self, sessions, frames):
         """Per-row codes (EOS-truncated, M:2280-2292) and last hidden states, host tensors."""
@@ -1226,7 +1464,7 @@ class TalkerEngine:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side), K.use_workspace(s.ws):
+        with torch.cuda.stream(side), K.use_workspace(s.ws), K.capturing():
             with torch.cuda.graph(g, stream=side):
                 self._prefill_compute(s, pre, B, P)
         torch.cuda.current_stream().wait_stream(side)
@@ -1279,7 +1517,7 @@ class TalkerEngine:
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side), K.use_workspace(s.ws):
+        with torch.cuda.stream(side), K.use_workspace(s.ws), K.capturing():
             with torch.cuda.graph(g, stream=side):
                 self._frame(s, part)
         torch.cuda.current_stream().wait_stream(side)
