@@ -10,6 +10,7 @@ Per-request state lives in a `Session` object, never on the module (fixes the re
 """
 from __future__ import annotations
 
+import contextlib
 import time
 from collections import OrderedDict, deque
 from dataclasses import dataclass
@@ -19,6 +20,7 @@ import torch
 
 from . import _hip
 from . import kernels as K
+from .feed import TextFeedTimeout
 
 
 def _to_dev_i32(ids, dev) -> torch.Tensor:
@@ -308,27 +310,22 @@ def _attn_oproj_ok(st: _Stack) -> bool:
 
 
 class CPLane:
-    """Buffers of a session's code predictor (rows [b0, b1) = the whole batch): the chain of the 15 sequential CP
-    steps of one frame.  (Round 2 also ran half-batch lanes on forked streams inside the frame graph; graph branches
-    do not overlap on this stack and the split measured slower -- 156.5 vs 167.0 audio-s/s -- so it was removed.)"""
+    """Buffers of a session's code predictor, the whole batch: the chain of the 15 sequential CP steps of one frame.
+    (Half-batch lanes on forked streams inside the frame graph measured slower -- 156.5 vs 167.0 audio-s/s: graph
+    branches do not overlap on this stack.)"""
 
-    def __init__(self, s: "Session", eng: "TalkerEngine", b0: int, b1: int, ws):
+    def __init__(self, s: "Session", eng: "TalkerEngine"):
         c, dev = eng.cp, eng.dev
-        self.b0, self.b1, self.nb = b0, b1, b1 - b0
-        nb = self.nb
+        self.nb = nb = s.B
         i32 = lambda *z: torch.zeros(*z, dtype=torch.int32, device=dev)  # noqa: E731
-        # prefill rows (2r, 2r + 1) = (past_hidden, cb0 embedding); decode rows 0..nb-1 of the same slice
-        self.x = s.cp_x[2 * b0:2 * b1]
-        self.x16 = None if s.cp_x16 is None else s.cp_x16[2 * b0:2 * b1]
-        self.kv = ([k[b0:b1] for k in s.cp_kv[0]], [v[b0:b1] for v in s.cp_kv[1]])
+        # prefill rows (2r, 2r + 1) = (past_hidden, cb0 embedding); decode rows 0..nb-1 of the same buffer
+        self.x, self.x16, self.kv = s.cp_x, s.cp_x16, s.cp_kv
         self.sc = _scratch(2 * nb, c, dev, attn_oproj=nb <= ATTN_OPROJ_MAX)
-        self.ws = ws
         # the step engine's hand-off granules + launch counter (zeroed once, kept across launches)
         self.ce_ws = (torch.zeros(K.cp_step_ws_bytes(), dtype=torch.uint8, device=dev)
                       if eng.cp_engine and nb <= 8 else None)
         self.logits = torch.zeros(nb, eng.Vc, dtype=torch.float32, device=dev)
-        self.tok = s.cp_tok[b0:b1]
-        self.codes = s.codes[b0:b1]
+        self.tok, self.codes = s.cp_tok, s.codes
         rb2 = torch.arange(2 * nb, device=dev, dtype=torch.int32) // 2
         p2 = torch.arange(2 * nb, device=dev, dtype=torch.int32) % 2
         self.meta0 = {"rope_pos": p2, "kv_pos": p2.clone(), "row_len": p2 + 1, "row_start": i32(2 * nb),
@@ -494,7 +491,7 @@ class Session:
         self.busy = False  # held by a live decode_iter (a suspended stream() generator included)
         self.watch = None  # HandoffWatch armed at the last yield of decode_iter
         self.txt = None    # text-append buffers + captured append graph (TalkerEngine.append_text), built on first use
-        self.cp = CPLane(self, eng, 0, B, self.ws)
+        self.cp = CPLane(self, eng)
 
 
 class TextGate:
@@ -547,6 +544,62 @@ class TextGate:
     def ready(self, f: int) -> bool:
         """Frame replay f (it reads trailing[b, f]) may be queued."""
         return all(self.row_ready(b, f) for b in range(len(self.n)))
+
+
+class _OpenGate:
+    """The gate of a request whose whole text is in its prompt: nothing to drain, every replay may be queued."""
+
+    def bind(self, eng, s, max_frames: int, use_graph: bool):
+        pass
+
+    def poll(self, f: int = 0):
+        pass
+
+    def ready(self, f: int) -> bool:
+        return True
+
+
+class SlotTable:
+    """The host's account of a continuous-batching run (serve / serve_iter): which request each batch row decodes,
+    since which frame replay, and what is still queued.  Plain Python, no device state.
+
+    prompt_lens[i], caps[i]: request i's prompt length and its frame cap (None: max_frames).  The first B = min(slots,
+    n) requests start together, left-padded to the longest of them; the others wait in `queue`, first in first out."""
+
+    def __init__(self, prompt_lens, caps, slots: int, max_frames: int):
+        self.n = n = len(prompt_lens)
+        self.B = B = max(1, min(slots, n)) if n else 0
+        self.lens = [int(p) for p in prompt_lens]
+        self.P = max(self.lens, default=0)              # the longest prompt: the session's capacity
+        self.cap = [max_frames if c is None else min(max_frames, int(c)) for c in caps]
+        self.queue = deque(range(B, n))
+        self.req = list(range(B))                       # request in each row, -1: idle
+        self.start = [0] * B                            # frame replays issued when the row's request started
+        self.slot_p = [max(self.lens[:B], default=0)] * B   # K/V rows before the request's first frame
+        self.frame = 0                                  # frame replays issued so far
+
+    def busy(self):
+        return [b for b in range(self.B) if self.req[b] >= 0]
+
+    def frames(self, b: int) -> int:
+        """Frames of row b's request issued so far, at most its cap."""
+        return min(self.frame - self.start[b], self.cap[self.req[b]])
+
+    def capped(self, b: int) -> bool:
+        """Row b's request has reached its frame cap: known on the host without asking the device."""
+        return self.frame - self.start[b] >= self.cap[self.req[b]]
+
+    def keys(self) -> int:
+        """Bound on the cached keys any busy row holds in the next frame replay."""
+        return max(self.slot_p[b] + self.frame - self.start[b] + 1 for b in range(self.B) if self.req[b] >= 0)
+
+    def retire(self, b: int) -> int:
+        """Row b's request is over: the row takes the next queued request (returned), or goes idle (-1)."""
+        self.start[b] = self.frame
+        i = self.req[b] = self.queue.popleft() if self.queue else -1
+        if i >= 0:
+            self.slot_p[b] = self.lens[i]
+        return i
 
 
 class TalkerEngine:
@@ -735,17 +788,17 @@ class TalkerEngine:
         K.advance_rows(s.ctr, B, 5, s.max_frames)
 
     def _cp_lane(self, s: Session, ln: CPLane):
-        """Code predictor for rows [b0, b1): 2-token prefill + 14 decode steps (M:1671-1680)."""
+        """Code predictor of the whole batch: 2-token prefill + 14 decode steps (M:1671-1680)."""
         t, c = self.talker, self.cp
         Hc, nb = c.H, ln.nb
         # --- prefill: rows (2r, 2r+1) = (past_hidden[r], codec_embedding(tok0[r])); the odd rows were written by
         # the talker sampler that chose tok0 (projected embedding table)
         if self.s2m is not None:
-            K.gemm(s.past_hidden[ln.b0:ln.b1], self.s2m, ln.x, nb, t.H, 2 * Hc, out2=ln.x16)
+            K.gemm(s.past_hidden, self.s2m, ln.x, nb, t.H, 2 * Hc, out2=ln.x16)
         else:
-            ln.x.view(nb, 2, Hc)[:, 0].copy_(s.past_hidden[ln.b0:ln.b1])
+            ln.x.view(nb, 2, Hc)[:, 0].copy_(s.past_hidden)
             if ln.x16 is not None:
-                ln.x16.view(nb, 2, Hc)[:, 0].copy_(s.past_hidden[ln.b0:ln.b1])
+                ln.x16.view(nb, 2, Hc)[:, 0].copy_(s.past_hidden)
         fuse = ln.ce_ws is not None and CP_FUSE_SAMPLE and self.Vc <= 2048
         pending = None  # the token choice the next step's launch makes first (fused)
         if ln.ce_ws is not None and CP_PREFILL:  # every layer + lm_head[0] for both positions in one launch
@@ -783,20 +836,19 @@ class TalkerEngine:
     def _cp_sample(self, s: Session, ln: CPLane, g, launch=True):
         c, gp = self.cp, s.gp
         if s.rows_c is not None:
-            how = {"rows": s.rows_c[ln.b0:ln.b1]}
+            how = {"rows": s.rows_c}
         else:
             how = {"do_sample": gp.subtalker_dosample, "top_k": gp.subtalker_top_k, "top_p": gp.subtalker_top_p,
                    "temperature": gp.subtalker_temperature, "seed_ptr": s.seed}
         return K.sample(ln.logits, ln.nb, self.Vc, self.Vc, ln.tok, **how,
-                 step=s.step[ln.b0:ln.b1], substep=1 + g, codes=ln.codes,
+                 step=s.step, substep=1 + g, codes=ln.codes,
                  codes_ld=s.codes.shape[1] * self.G, codes_w=self.G, codes_col=1 + g, codes_step_off=0, ctr_stride=1,
-                 philox_row=s.prow[ln.b0:ln.b1],
+                 philox_row=s.prow,
                  emb=(self.cp_in_tabs[g], ln.x, c.H) if g < self.G - 2 else None,
                  emb16=(ln.x16, c.H) if ln.x16 is not None and g < self.G - 2 else None,
                  emb2=(self.cp_qkv_tabs[g], ln.sc["qkv"], c.qkv_w) if self.cp_qkv_tabs is not None and g < self.G - 2
                  else None,
-                 force=None if s.force is None else s.force[ln.b0:ln.b1],
-                 pick=None if s.pick is None else s.pick[ln.b0:ln.b1], launch=launch)
+                 force=s.force, pick=s.pick, launch=launch)
 
     # ---------------------------------------------------------------- G2/G3: prefill + decode loop
     def generate_from_embeds(self, embeds: torch.Tensor, mask: torch.Tensor, trailing: torch.Tensor,
@@ -852,98 +904,37 @@ class TalkerEngine:
         complete -- after its code predictor, before the talker step that starts frame 1 (which is queued after the
         caller's work, e.g. the first codec window); at that yield codes[:, 1, 0] is not written yet (EOS cannot occur
         there anyway: it is masked below min_new_tokens).  gate (streaming-text input): a TextGate asked
-        before every frame replay whether the text position that replay reads has arrived (_frames_gated)."""
+        before every frame replay whether the text position that replay reads has arrived (_frames)."""
         B, P, H = embeds.shape
         gp.check_rows(B)
         max_frames = max(gp.max_new_tokens - 1, 0)
         seed = gp.resolve_seed()
-        main = torch.cuda.current_stream(self.dev)
+        gate = _OpenGate() if gate is None else gate
         sessions = []
         try:
             s = self.session(B, P, max(max_frames, 1), gp)
             sessions.append(s)
             with K.use_workspace(s.ws):
                 self._prefill(s, embeds, mask, trailing, tts_pad, seed, philox_ids, gp=gp)
-            if gate is not None:
-                gate.bind(self, s, max_frames, use_graph)
-            yield from self._frames(sessions, [main], max_frames, use_graph, on_frames, every, first, grow, early_first,
-                                    gate)
+            gate.bind(self, s, max_frames, use_graph)
+            yield from self._frames(s, max_frames, use_graph, on_frames, every, first, grow, early_first, gate)
         finally:
             self.release(sessions)
 
-    def _frames(self, sessions, streams, max_frames, use_graph, on_frames, every, first, grow=False, early_first=False,
-                gate=None):
-        if gate is not None:  # streaming-text input: a loop of its own, so that this one stays as it is
-            yield from self._frames_gated(sessions[0], max_frames, use_graph, on_frames, every, first, grow,
-                                          early_first, gate)
-            return
-        main = torch.cuda.current_stream(self.dev)
-        frames = 0
-        check_every = 8
-        next_yield = first or every
-        interval = max(first - 1, 1)
-        for s, st in zip(sessions, streams):
-            with torch.cuda.stream(st):
-                s.hiddens[:, 0].copy_(s.past_hidden)  # later frames are recorded inside the frame graph
-        # EOS polling without a host sync: every `check_every` frames the all-finished flag is copied to pinned
-        # memory behind an event; the copy from the previous window is read once its event has completed
-        pending = []
-        watch = None  # hand-off flags as of the previous yield (checked before the next chunk is handed out)
-        while frames < max_frames:
-            early = early_first and frames == 0 and next_yield == 1 and max_frames > 1
-            for s, st in zip(sessions, streams):
-                with torch.cuda.stream(st):  # every row holds <= P + frames + 1 keys
-                    self._run_frame(s, s.P + frames + 1, use_graph, "cp" if early else "all")
-            frames += 1
-            if on_frames is not None:
-                on_frames(sessions[0], frames)
-            if next_yield and frames == next_yield and frames < max_frames:
-                for st in streams:
-                    main.wait_stream(st)
-                if watch is not None:  # the caller consumed the previous chunk: those frames are done
-                    watch.check()
-                with torch.cuda.stream(main):
-                    watch = HandoffWatch(sessions)
-                for s in sessions:  # a caller that synchronised on these frames checks it before using them
-                    s.watch = watch
-                yield sessions, frames, False
-                interval = min(every, 2 * interval) if grow else every
-                next_yield = frames + interval if every else 0
-            if early:  # the rest of frame 0 (talker step -> cb0 of frame 1), behind the caller's work
-                for s, st in zip(sessions, streams):
-                    with torch.cuda.stream(st):
-                        self._run_frame(s, s.P + 1, use_graph, "talk")
-            if frames % check_every == 0 and frames < max_frames:
-                flags = []
-                for s, st in zip(sessions, streams):
-                    with torch.cuda.stream(st):
-                        f = torch.empty(1, dtype=torch.bool, pin_memory=True)
-                        f.copy_(s.finished.all().reshape(1), non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(st)
-                        flags.append((f, ev))
-                pending.append(flags)
-                done = False
-                while pending and all(ev.query() for _, ev in pending[0]):
-                    if all(bool(f.item()) for f, _ in pending.pop(0)):
-                        done = True
-                if done:
-                    break
-        for st in streams:
-            main.wait_stream(st)
-        check_handoffs(sessions)
-        yield sessions, frames, True
+    def _frames(self, s: Session, max_frames, use_graph, on_frames, every, first, grow, early_first, gate):
+        """The frame loop of decode_iter, for one session.  Frame replay f reads trailing[b, f], so it is queued only
+        once gate.ready(f): every row that is neither closed nor known finished has a text token there (a request
+        whose text is all in its prompt has an _OpenGate, which is always ready).  The gate drains its feed (no
+        blocking) before every replay.  A one-frame first chunk needs no text at all: frame 0's codes come from the
+        prefill and the code predictor (the early_first split: "cp", yield, then "talk"); only the talk half of
+        replay 0 waits.  When no replay can be queued the loop, in this order, reports every frame finished so far
+        (whatever `every` says), synchronises and reads the rows' finished flags (all finished: the stream ends
+        normally, text closed or not), and waits for the feed up to its timeout, then raises TextFeedTimeout.
 
-    def _frames_gated(self, s: Session, max_frames, use_graph, on_frames, every, first, grow, early_first, gate):
-        """_frames for one session whose trailing text arrives while it decodes.  Frame replay f reads
-        trailing[b, f], so it is queued only once gate.ready(f): every row that is neither closed nor known finished
-        has a text token there.  The gate drains its feed (no blocking) before every replay.  A one-frame first chunk
-        needs no text at all: frame 0's codes come from the prefill and the code predictor (the early_first split);
-        only the talk half of replay 0 waits.  When no replay can be queued the loop, in this order, reports every
-        frame finished so far (whatever `every` says), synchronises and reads the rows' finished flags (all finished:
-        the stream ends normally, text closed or not), and waits for the feed up to its timeout, then raises
-        TextFeedTimeout.  Yields as _frames does."""
-        from .feed import TextFeedTimeout
+        Every frame is issued, and every HandoffWatch armed, on the stream that was current when the generator was
+        first resumed, whatever stream is current at a later resume (concurrent requests are resumed under
+        `with torch.cuda.stream(...)`).  Every caller that passes a TextGate resumes on one stream."""
+        main = torch.cuda.current_stream(self.dev)
         sessions = [s]
         frames = 0            # frames whose 16 codes are complete
         reported = 0          # ... as of the last yield
@@ -953,38 +944,42 @@ class TalkerEngine:
         check_every = 8
         next_yield = first or every
         interval = max(first - 1, 1)
-        s.hiddens[:, 0].copy_(s.past_hidden)
+        with torch.cuda.stream(main):
+            s.hiddens[:, 0].copy_(s.past_hidden)  # later frames are recorded inside the frame graph
+        # EOS polling without a host sync: every `check_every` frames the all-finished flag is copied to pinned
+        # memory behind an event; the copy from the previous window is read once its event has completed
         pending = []
-        watch = None
+        watch = None  # hand-off flags as of the previous yield (checked before the next chunk is handed out)
 
         def report():
-            nonlocal watch
-            if watch is not None:
+            nonlocal watch, reported
+            reported = frames
+            if watch is not None:  # the caller consumed the previous chunk: those frames are done
                 watch.check()
-            watch = s.watch = HandoffWatch(sessions)
+            with torch.cuda.stream(main):  # a caller that synchronised on these frames checks it before using them
+                watch = s.watch = HandoffWatch(sessions)
             return sessions, frames, False
 
         while frames < max_frames:
-            gate.poll(0 if talk_due else frames)
-            if early_first and frames == 0 and not talk_due and next_yield == 1 and max_frames > 1:
-                self._run_frame(s, s.P + 1, use_graph, "cp")  # no text position is read
-                frames, talk_due = 1, True
-                if on_frames is not None:
-                    on_frames(s, frames)
-                reported = frames
-                yield report()
-                interval = min(every, 2 * interval) if grow else every
-                next_yield = frames + interval if every else 0
-                continue
             f = 0 if talk_due else frames  # the replay to queue, i.e. the trailing position it reads
-            if not gate.ready(f):
+            with torch.cuda.stream(main):
+                gate.poll(f)
+                if early_first and frames == 0 and not talk_due and next_yield == 1 and max_frames > 1:
+                    part = "cp"  # frame 0's code predictor: no text position is read
+                elif not gate.ready(f):
+                    part = None
+                else:  # "talk": the rest of frame 0 (talker step -> cb0 of frame 1), behind the caller's work
+                    part = "talk" if talk_due else "all"
+                if part is not None:  # every row holds <= P + f + 1 keys
+                    self._run_frame(s, s.P + f + 1, use_graph, part)
+            if part is None:
                 if frames > reported:  # the listener gets all audio that exists
-                    reported = frames
                     yield report()
                     continue
                 if flags_at != (frames, talk_due):
                     flags_at = (frames, talk_due)
-                    fin = s.finished.cpu()  # (synchronises)
+                    with torch.cuda.stream(main):
+                        fin = s.finished.cpu()  # (synchronises)
                     gate.finished = [bool(x) for x in fin.tolist()]
                     if all(gate.finished):
                         break
@@ -999,24 +994,22 @@ class TalkerEngine:
                         f"have {[gate.n[b] for b in range(s.B) if not gate.row_ready(b, f)]} trailing tokens")
                 continue
             deadline = None
-            if talk_due:
-                self._run_frame(s, s.P + 1, use_graph, "talk")
-                talk_due = False
+            talk_due = part == "cp"
+            if part == "talk":
                 continue
-            self._run_frame(s, s.P + frames + 1, use_graph)
             frames += 1
             if on_frames is not None:
                 on_frames(s, frames)
             if next_yield and frames == next_yield and frames < max_frames:
-                reported = frames
                 yield report()
                 interval = min(every, 2 * interval) if grow else every
                 next_yield = frames + interval if every else 0
             if frames % check_every == 0 and frames < max_frames:
-                fl = torch.empty(1, dtype=torch.bool, pin_memory=True)
-                fl.copy_(s.finished.all().reshape(1), non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
+                with torch.cuda.stream(main):
+                    fl = torch.empty(1, dtype=torch.bool, pin_memory=True)
+                    fl.copy_(s.finished.all().reshape(1), non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record(main)
                 pending.append((fl, ev))
                 done = False
                 while pending and pending[0][1].query():
@@ -1096,15 +1089,8 @@ class TalkerEngine:
                 with K.use_workspace(s.ws):
                     self._append_compute(s)
                 continue
-            if tx["graph"] is None:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(side), K.use_workspace(s.ws), K.capturing():
-                    with torch.cuda.graph(g, stream=side):
-                        self._append_compute(s)
-                torch.cuda.current_stream().wait_stream(side)
-                tx["graph"] = g
+            if tx["graph"] is None:  # (it touches no per-request state of the session)
+                tx["graph"] = self._capture(s, lambda: self._append_compute(s), keep_state=False)
             tx["graph"].replay()
 
     def collect(self, sessions, frames):
@@ -1143,102 +1129,112 @@ class TalkerEngine:
         a single-request prefill into the slot's K/V rows between two graph replays.  The host learns which rows
         ended from pinned copies of the device flags every `poll` frames (no host sync on the decode stream).
         philox_ids: optional Philox stream id per request (default its index i)."""
+        with self._serving(requests, tts_pad, gp, slots, philox_ids) as run:
+            if run is None:
+                return
+            s, tab, refill = run
+            B, H, dev = tab.B, self.talker.H, self.dev
+            ahead = 1
+            eos = self.tc["codec_eos_token_id"]
+            epoch = [0] * B
+            polls, harvests = [], []
+            while (busy := tab.busy()) or harvests:
+                if busy:
+                    self._run_frame(s, min(tab.keys(), s.Lmax), use_graph)
+                    tab.frame += 1
+                    if tab.frame % poll == 0 and not gp.ignore_eos:  # (with ignore_eos only frame counts end rows)
+                        st = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
+                        st[:B].copy_(s.step, non_blocking=True)
+                        st[B:].copy_(s.finished, non_blocking=True)
+                        ev = torch.cuda.Event()
+                        ev.record()
+                        polls.append((st, list(epoch), ev))
+                else:  # only harvests left in flight
+                    harvests[0][-1].synchronize()
+                # rows that ended (as of a completed poll, same request still in the slot): copy their codes out
+                # and refill the slot, both in stream order behind the frames already queued.  The host may run
+                # at most `ahead` polls in front of the GPU (else it would queue many frames past a row's end
+                # before seeing it, and that row's slot would idle for all of them)
+                ended = [b for b in busy if tab.capped(b)]
+                while polls and (len(polls) > ahead or polls[0][2].query()):
+                    polls[0][2].synchronize()
+                    st, ep, _ = polls.pop(0)
+                    ended += [b for b in busy if ep[b] == epoch[b] and int(st[B + b])]
+                # a row whose request reached its frame count is known on the host without a poll (its frame
+                # index = frames replayed since it started); EOS is learned from the polls
+                for b in sorted(set(ended)):
+                    hc = torch.empty(s.codes.shape[1], self.G, dtype=torch.int32, pin_memory=True)
+                    hh = torch.empty(s.hiddens.shape[1], H, dtype=torch.float32, pin_memory=True)
+                    hs = torch.empty(1, dtype=torch.int32, pin_memory=True)
+                    hc.copy_(s.codes[b], non_blocking=True)
+                    hh.copy_(s.hiddens[b], non_blocking=True)
+                    hs.copy_(s.step[b:b + 1], non_blocking=True)
+                    hf, fw = None, _flag_word(s)
+                    if fw is not None:  # the hand-off flags as of this request's last frame
+                        hf = torch.empty(1, dtype=torch.int32, pin_memory=True)
+                        hf.copy_(fw, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    harvests.append((tab.req[b], hc, hh, hs, hf, ev))
+                    epoch[b] += 1
+                    refill(b)
+                while harvests and harvests[0][-1].query():
+                    i, hc, hh, hs, hf, _ = harvests.pop(0)
+                    if hf is not None and int(hf[0]) != 0:  # never hand out a request decoded on stale partials
+                        # the flag is session-wide: every request in flight is suspect -- stop and report them
+                        torch.cuda.synchronize(dev)
+                        _clear_flags(s)
+                        failed = {i} | {h[0] for h in harvests} | {tab.req[b] for b in tab.busy()}
+                        raise HandoffError(failed, tab.queue)
+                    # frames [0, F) are final: F = the first EOS in cb0 (within the row's frame range), else the
+                    # row's frame count (max_new_tokens - 1)
+                    F = min(int(hs[0]), tab.cap[i])
+                    hit = (hc[:F + 1, 0] == eos).nonzero()
+                    F = int(hit[0]) if hit.numel() else F
+                    yield i, hc[:F].long(), hh[:F].clone()
+
+    @contextlib.contextmanager
+    def _serving(self, requests, tts_pad, gp: GenParams, slots: int, philox_ids):
+        """What a continuous-batching run is, however its progress is observed: the slot table, one session for
+        min(slots, n) rows started by a batched prefill, the refill of a row, and at a normal end the hand-off check
+        and `serve_stats`.  Yields (session, table, refill), or None for an empty request list (no session is taken);
+        the session is released when the block is left.  refill(b): row b's request is over -- in stream order behind
+        the frames already queued, the row starts the next queued request (its single-request prefill) or goes idle.
+        `serve_queued`: request -> host time at which its prefill was queued (tools/serve_bench.py --stream)."""
         n = len(requests)
         pids = list(range(n)) if philox_ids is None else [int(x) for x in philox_ids]
         gp.check_rows(n)
         if n == 0:
+            yield None
             return
-        B = max(1, min(slots, n))
-        ahead = 1
         max_frames = max(gp.max_new_tokens - 1, 1)
-        P = max(int(r[0].shape[0]) for r in requests)
-        cap_i = [min(max_frames, int(r[2])) if len(r) > 2 and r[2] is not None else max_frames for r in requests]
+        tab = SlotTable([r[0].shape[0] for r in requests], [r[2] if len(r) > 2 else None for r in requests], slots,
+                        max_frames)
         seed = gp.resolve_seed()
-        eos = self.tc["codec_eos_token_id"]
-        s = self.session(B, P, max_frames, gp)
-        H, dev = self.talker.H, self.dev
+        s = self.session(tab.B, tab.P, max_frames, gp)
+
+        def refill(b):
+            i = tab.retire(b)
+            if i >= 0:
+                self.serve_queued[i] = time.perf_counter()
+                self._prefill_slot(s, b, requests[i], pids[i], gp.row_records(i, seed) if gp.per_row else None)
+            else:
+                s.finished[b:b + 1].fill_(1)  # idle slot: emits EOS until the session ends
+
         try:
             with K.use_workspace(s.ws):
-                Pb = self._serve_start(s, requests, B, tts_pad, seed, pids, gp)
-                queue = list(range(B, n))
-                slot_req = list(range(B))
-                epoch = [0] * B
-                start = [0] * B  # host frame count when the slot's request started
-                slot_p = [Pb] * B  # prompt length (K/V rows before the first frame) of each slot's request
-                polls, harvests = [], []
-                frame = 0
-                while any(r >= 0 for r in slot_req) or harvests:
-                    if any(r >= 0 for r in slot_req):
-                        keys = max(slot_p[b] + frame - start[b] + 1 for b in range(B) if slot_req[b] >= 0)
-                        self._run_frame(s, min(keys, s.Lmax), use_graph)
-                        frame += 1
-                        if frame % poll == 0 and not gp.ignore_eos:  # (with ignore_eos only frame counts end rows)
-                            st = torch.empty(2 * B, dtype=torch.int32, pin_memory=True)
-                            st[:B].copy_(s.step, non_blocking=True)
-                            st[B:].copy_(s.finished, non_blocking=True)
-                            ev = torch.cuda.Event()
-                            ev.record()
-                            polls.append((st, list(epoch), ev))
-                    else:  # only harvests left in flight
-                        harvests[0][-1].synchronize()
-                    # rows that ended (as of a completed poll, same request still in the slot): copy their codes out
-                    # and refill the slot, both in stream order behind the frames already queued.  The host may run
-                    # at most `ahead` polls in front of the GPU (else it would queue many frames past a row's end
-                    # before seeing it, and that row's slot would idle for all of them)
-                    ended = [b for b in range(B) if slot_req[b] >= 0 and frame - start[b] >= cap_i[slot_req[b]]]
-                    while polls and (len(polls) > ahead or polls[0][2].query()):
-                        polls[0][2].synchronize()
-                        st, ep, _ = polls.pop(0)
-                        ended += [b for b in range(B) if slot_req[b] >= 0 and ep[b] == epoch[b] and int(st[B + b])]
-                    # a row whose request reached its frame count is known on the host without a poll (its frame
-                    # index = frames replayed since it started); EOS is learned from the polls
-                    for b in sorted(set(ended)):
-                        hc = torch.empty(s.codes.shape[1], self.G, dtype=torch.int32, pin_memory=True)
-                        hh = torch.empty(s.hiddens.shape[1], H, dtype=torch.float32, pin_memory=True)
-                        hs = torch.empty(1, dtype=torch.int32, pin_memory=True)
-                        hc.copy_(s.codes[b], non_blocking=True)
-                        hh.copy_(s.hiddens[b], non_blocking=True)
-                        hs.copy_(s.step[b:b + 1], non_blocking=True)
-                        hf, fw = None, _flag_word(s)
-                        if fw is not None:  # the hand-off flags as of this request's last frame
-                            hf = torch.empty(1, dtype=torch.int32, pin_memory=True)
-                            hf.copy_(fw, non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record()
-                        harvests.append((slot_req[b], hc, hh, hs, hf, ev))
-                        epoch[b] += 1
-                        start[b] = frame
-                        slot_req[b] = queue.pop(0) if queue else -1
-                        if slot_req[b] >= 0:
-                            slot_p[b] = int(requests[slot_req[b]][0].shape[0])
-                            self._prefill_slot(s, b, requests[slot_req[b]], pids[slot_req[b]],
-                                               gp.row_records(slot_req[b], seed) if gp.per_row else None)
-                        else:
-                            s.finished[b:b + 1].fill_(1)  # idle slot: emits EOS until the session ends
-                    while harvests and harvests[0][-1].query():
-                        i, hc, hh, hs, hf, _ = harvests.pop(0)
-                        if hf is not None and int(hf[0]) != 0:  # never hand out a request decoded on stale partials
-                            # the flag is session-wide: every request in flight is suspect -- stop and report them
-                            torch.cuda.synchronize(dev)
-                            _clear_flags(s)
-                            failed = {i} | {h[0] for h in harvests} | {r for r in slot_req if r >= 0}
-                            raise HandoffError(failed, queue)
-                        # frames [0, F) are final: F = the first EOS in cb0 (within the row's frame range), else the
-                        # row's frame count (max_new_tokens - 1)
-                        F = min(int(hs[0]), cap_i[i])
-                        hit = (hc[:F + 1, 0] == eos).nonzero()
-                        F = int(hit[0]) if hit.numel() else F
-                        yield i, hc[:F].long(), hh[:F].clone()
+                self.serve_queued = dict.fromkeys(range(tab.B), time.perf_counter())
+                self._serve_start(s, requests, tab.B, tab.slot_p[0], tts_pad, seed, pids, gp)
+                yield s, tab, refill
                 check_handoffs([s])
-                self.serve_stats = {"frames": frame, "slots": B, "requests": n}
+                self.serve_stats = {"frames": tab.frame, "slots": tab.B, "requests": n}
         finally:
             self.release([s])
 
-    def _serve_start(self, s: Session, requests, B, tts_pad, seed, pids, gp):
-        """The first B requests of a continuous-batching run start together: one left-padded batched prefill (as
-        generate() does).  Returns the padded prompt length."""
+    def _serve_start(self, s: Session, requests, B, Pb, tts_pad, seed, pids, gp):
+        """The first B requests of a continuous-batching run start together: one batched prefill, left-padded to Pb
+        tokens (as generate() does)."""
         H, dev = self.talker.H, self.dev
-        Pb = max(int(r[0].shape[0]) for r in requests[:B])
         Tb = max(int(r[1].shape[0]) for r in requests[:B])
         emb = torch.zeros(B, Pb, H, dtype=torch.float32, device=dev)
         mask = torch.zeros(B, Pb, dtype=torch.long, device=dev)
@@ -1250,7 +1246,6 @@ class TalkerEngine:
             trail[b, :tr.shape[0]] = tr
         self._prefill(s, emb, mask, trail, tts_pad, seed, pids[:B], gp=gp)
         s.hiddens[:, 0].copy_(s.past_hidden)
-        return Pb
 
     def serve_iter(self, requests, tts_pad, gp: GenParams, slots: int = 8, use_graph: bool = True, every: int = 8,
                    first: int = 1, philox_ids=None):
@@ -1265,74 +1260,46 @@ class TalkerEngine:
         order before it resumes the generator, which then refills the ended slots.  One host sync per report (the
         cb0 columns of the new frames and the hand-off flag word, copied together): a hand-off give-up raises
         HandoffError before the frames it covers are reported."""
-        n = len(requests)
-        pids = list(range(n)) if philox_ids is None else [int(x) for x in philox_ids]
-        gp.check_rows(n)
-        if n == 0:
-            return
-        B = max(1, min(slots, n))
-        max_frames = max(gp.max_new_tokens - 1, 1)
-        P = max(int(r[0].shape[0]) for r in requests)
-        cap_i = [min(max_frames, int(r[2])) if len(r) > 2 and r[2] is not None else max_frames for r in requests]
-        seed = gp.resolve_seed()
-        eos = self.tc["codec_eos_token_id"]
-        s = self.session(B, P, max_frames, gp)
-        try:
-            with K.use_workspace(s.ws):
-                # request -> host time at which its prefill was queued (tools/serve_bench.py --stream)
-                self.serve_queued = dict.fromkeys(range(B), time.perf_counter())
-                Pb = self._serve_start(s, requests, B, tts_pad, seed, pids, gp)
-                queue = list(range(B, n))
-                slot_req = list(range(B))
-                start = [0] * B      # host frame count when the slot's request started
-                slot_p = [Pb] * B    # prompt length of each slot's request
-                seen = [0] * B       # frames of the slot's request already reported
-                fresh = [True] * B   # the slot's request has not been reported yet
-                frame, last_report = 0, 0
-                while any(r >= 0 for r in slot_req):
-                    busy = [b for b in range(B) if slot_req[b] >= 0]
-                    keys = max(slot_p[b] + frame - start[b] + 1 for b in busy)
-                    self._run_frame(s, min(keys, s.Lmax), use_graph)
-                    frame += 1
-                    if not (frame - last_report >= every or any(fresh[b] and frame - start[b] >= first for b in busy)):
-                        continue
-                    last_report = frame
-                    # frames [0, k_b) of slot b are final and column k_b holds its next cb0 (EOS of an ending request)
-                    k = [min(frame - start[b], cap_i[slot_req[b]]) if slot_req[b] >= 0 else 0 for b in range(B)]
-                    c0 = torch.empty(B, max(k) + 1, dtype=torch.int32, pin_memory=True)
-                    c0.copy_(s.codes[:, :max(k) + 1, 0], non_blocking=True)
-                    fw = _flag_word(s)
-                    hf = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                    if fw is not None:
-                        hf.copy_(fw, non_blocking=True)
-                    torch.cuda.current_stream(self.dev).synchronize()
-                    if int(hf[0]) != 0:  # session-wide and sticky: every request in flight is suspect
-                        _clear_flags(s)
-                        raise HandoffError({r for r in slot_req if r >= 0}, queue)
-                    report = [None] * B
-                    for b in busy:
-                        hit = (c0[b, seen[b]:k[b] + 1] == eos).nonzero()
-                        f = seen[b] + int(hit[0]) if hit.numel() else k[b]
-                        ended = bool(hit.numel()) or k[b] >= cap_i[slot_req[b]]
-                        report[b] = (slot_req[b], seen[b], f, ended, int((c0[b, seen[b]:f] != 0).sum()))
-                        seen[b], fresh[b] = f, False
-                    yield s, report
-                    for b in busy:
-                        if not report[b][3]:
-                            continue
-                        start[b], seen[b], fresh[b] = frame, 0, True
-                        slot_req[b] = queue.pop(0) if queue else -1
-                        if slot_req[b] >= 0:
-                            self.serve_queued[slot_req[b]] = time.perf_counter()
-                            slot_p[b] = int(requests[slot_req[b]][0].shape[0])
-                            self._prefill_slot(s, b, requests[slot_req[b]], pids[slot_req[b]],
-                                               gp.row_records(slot_req[b], seed) if gp.per_row else None)
-                        else:
-                            s.finished[b:b + 1].fill_(1)  # idle slot: emits EOS until the session ends
-                check_handoffs([s])
-                self.serve_stats = {"frames": frame, "slots": B, "requests": n}
-        finally:
-            self.release([s])
+        with self._serving(requests, tts_pad, gp, slots, philox_ids) as run:
+            if run is None:
+                return
+            s, tab, refill = run
+            B = tab.B
+            eos = self.tc["codec_eos_token_id"]
+            seen = [0] * B       # frames of the slot's request already reported
+            fresh = [True] * B   # the slot's request has not been reported yet
+            last_report = 0
+            while busy := tab.busy():
+                self._run_frame(s, min(tab.keys(), s.Lmax), use_graph)
+                tab.frame += 1
+                if not (tab.frame - last_report >= every
+                        or any(fresh[b] and tab.frame - tab.start[b] >= first for b in busy)):
+                    continue
+                last_report = tab.frame
+                # frames [0, k_b) of slot b are final and column k_b holds its next cb0 (EOS of an ending request)
+                k = [tab.frames(b) if tab.req[b] >= 0 else 0 for b in range(B)]
+                c0 = torch.empty(B, max(k) + 1, dtype=torch.int32, pin_memory=True)
+                c0.copy_(s.codes[:, :max(k) + 1, 0], non_blocking=True)
+                fw = _flag_word(s)
+                hf = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+                if fw is not None:
+                    hf.copy_(fw, non_blocking=True)
+                torch.cuda.current_stream(self.dev).synchronize()
+                if int(hf[0]) != 0:  # session-wide and sticky: every request in flight is suspect
+                    _clear_flags(s)
+                    raise HandoffError({tab.req[b] for b in busy}, tab.queue)
+                report = [None] * B
+                for b in busy:
+                    hit = (c0[b, seen[b]:k[b] + 1] == eos).nonzero()
+                    f = seen[b] + int(hit[0]) if hit.numel() else k[b]
+                    ended = bool(hit.numel()) or tab.capped(b)
+                    report[b] = (tab.req[b], seen[b], f, ended, int((c0[b, seen[b]:f] != 0).sum()))
+                    seen[b], fresh[b] = f, False
+                yield s, report
+                for b in busy:
+                    if report[b][3]:
+                        seen[b], fresh[b] = 0, True
+                        refill(b)
 
     def _prefill_slot(self, s: Session, b: int, req, i: int, records=None):
         """Start a request in batch row b (Philox stream id i): per-row state reset, single-request talker prefill into
@@ -1364,11 +1331,8 @@ class TalkerEngine:
         if pre is None:
             i32 = lambda *z: torch.zeros(*z, dtype=torch.int32, device=dev)  # noqa: E731
             ar = torch.arange(P, device=dev, dtype=torch.int32)
-            pre = {"x": torch.empty(P, H, dtype=torch.float32, device=dev), "sc": _scratch(P, t, dev),
-                   "meta": {"rope_pos": ar, "kv_pos": ar.clone(), "row_len": ar + 1, "row_start": i32(P),
-                            "row_batch": i32(P)},
-                   "x16": (torch.empty(P, H, dtype=torch.bfloat16, device=dev)
-                           if X16 and self.wdt == torch.bfloat16 and (P <= 96 or PF) else None)}
+            pre = self._prefill_buffers(P, {"rope_pos": ar, "kv_pos": ar.clone(), "row_len": ar + 1,
+                                            "row_start": i32(P), "row_batch": i32(P)})
             _lru_put(s.slot_prefill, P, pre)
         pre["meta"]["row_batch"].fill_(b)
         pre["x"].copy_(emb.reshape(P, H))
@@ -1385,7 +1349,6 @@ class TalkerEngine:
         philox_ids: per-row Philox stream ids (default the row index).  gp: the call's parameters -- a per-row
         session's tables get the records of requests 0 .. B-1 before the first sample."""
         B, P, H = embeds.shape
-        t = self.talker
         dev = self.dev
         s.P = P  # padded prompt length: every row's decode keys are <= P + frames + 1
         # reset per-request state
@@ -1418,15 +1381,11 @@ class TalkerEngine:
         pre = _lru_get(s.prefill, P)
         if pre is None:  # static buffers of this prompt length (a captured graph binds their addresses)
             i32 = lambda *z: torch.zeros(*z, dtype=torch.int32, device=dev)  # noqa: E731
-            pre = {"x": torch.empty(R, H, dtype=torch.float32, device=dev), "sc": _scratch(R, t, dev),
-                   "meta": {"rope_pos": i32(R), "kv_pos": torch.arange(P, device=dev, dtype=torch.int32).repeat(B),
-                            "row_len": torch.arange(1, P + 1, device=dev, dtype=torch.int32).repeat(B),
-                            "row_start": i32(R),
-                            "row_batch": torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(P)},
-                   "last": torch.empty(B, H, dtype=torch.float32, device=dev), "graph": None, "uses": 0,
-                   # bf16 shadow of the prefill residual (skinny-GEMV row counts): the RMS GEMVs read half the bytes
-                   "x16": (torch.empty(R, H, dtype=torch.bfloat16, device=dev)
-                           if X16 and self.wdt == torch.bfloat16 and (R <= 96 or PF) else None)}
+            pre = self._prefill_buffers(R, {
+                "rope_pos": i32(R), "kv_pos": torch.arange(P, device=dev, dtype=torch.int32).repeat(B),
+                "row_len": torch.arange(1, P + 1, device=dev, dtype=torch.int32).repeat(B), "row_start": i32(R),
+                "row_batch": torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(P)})
+            pre.update(last=torch.empty(B, H, dtype=torch.float32, device=dev), graph=None, uses=0)
             _lru_put(s.prefill, P, pre)
         pre["meta"]["rope_pos"].copy_(pos.reshape(-1))
         pre["meta"]["row_start"].copy_(torch.where(mask.bool(), n_pads[:, None], torch.zeros_like(n_pads)[:, None])
@@ -1440,13 +1399,22 @@ class TalkerEngine:
             # a prompt length seen twice (streaming-text prompts repeat it: role + codec prefix) gets a captured
             # prefill: ~170 launches replayed instead of issued from Python (host-bound, ~4.6 ms at B=8)
             if PREFILL_GRAPH and pre["uses"] >= 2:
-                pre["graph"] = self._capture_prefill(s, pre, B, P)
+                pre["graph"] = self._capture(s, lambda: self._prefill_compute(s, pre, B, P))
         # decode counters: step 0, one token generated, pos = P + delta, kv_pos = P, len = P + 1
         s.n_gen.fill_(1)  # a device fill: item assignment uploads a host scalar and waits for the prefill
         s.meta["rope_pos"].copy_((P + rope_delta).to(torch.int32))
         s.meta["kv_pos"].fill_(P)
         s.meta["row_len"].fill_(P + 1)
         s.meta["row_start"].copy_(n_pads.to(torch.int32))
+
+    def _prefill_buffers(self, R: int, meta: dict) -> dict:
+        """Static buffers of a talker prefill over R rows: the fp32 residual stream, the scratch, the row arrays the
+        caller built, and in bf16 mode the residual's bf16 shadow, which the RMS GEMMs read at half the bytes (at
+        the row counts whose linears keep it current: the skinny GEMVs, and gemm_pf_k at any count)."""
+        t, dev = self.talker, self.dev
+        use16 = X16 and self.wdt == torch.bfloat16 and (R <= 96 or PF)
+        return {"x": torch.empty(R, t.H, dtype=torch.float32, device=dev), "sc": _scratch(R, t, dev), "meta": meta,
+                "x16": torch.empty(R, t.H, dtype=torch.bfloat16, device=dev) if use16 else None}
 
     def _prefill_compute(self, s: Session, pre, B, P):
         """The talker prefill forward over static buffers, then the first token (graph-capturable)."""
@@ -1458,19 +1426,6 @@ class TalkerEngine:
         K.rmsnorm(pre["last"], t.norm, t.eps, s.past_hidden, B, H)
         K.gemm(s.past_hidden, self.codec_head, s.logits, B, H, self.V)
         self._sample_talker(s, s.logits, 0, 99)
-
-    def _capture_prefill(self, s: Session, pre, B, P):
-        snap = s.ctr.clone(), s.seen.clone(), s.finished.clone(), s.codes.clone(), s.tok0.clone(), s.seed.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side), K.use_workspace(s.ws), K.capturing():
-            with torch.cuda.graph(g, stream=side):
-                self._prefill_compute(s, pre, B, P)
-        torch.cuda.current_stream().wait_stream(side)
-        s.ctr.copy_(snap[0]); s.seen.copy_(snap[1]); s.finished.copy_(snap[2]); s.codes.copy_(snap[3])
-        s.tok0.copy_(snap[4]); s.seed.copy_(snap[5])
-        return g
 
     def _run_frame(self, s: Session, keys: int, use_graph: bool = True, part: str = "all"):
         """One frame of session s whose rows hold at most `keys` cached talker keys (a host-side bound): the talker
@@ -1487,7 +1442,7 @@ class TalkerEngine:
             return
         g = s.graphs.get((ns, part))
         if g is None:
-            g = s.graphs[(ns, part)] = self._capture(s, part)
+            g = s.graphs[(ns, part)] = self._capture(s, lambda: self._frame(s, part))
         if part == "all":
             s.graph = g
         self._fence_in()
@@ -1511,17 +1466,19 @@ class TalkerEngine:
         ev.record(cur)
         self._fence = (ev, cur)
 
-    def _capture(self, s: Session, part: str = "all"):
-        # the graph must not see the prefill-time counter values: it only reads device memory
-        snap = s.ctr.clone(), s.seen.clone(), s.finished.clone(), s.codes.clone(), s.tok0.clone(), s.seed.clone()
+    def _capture(self, s: Session, fn, keep_state: bool = True):
+        """fn() captured into a HIP graph on a side stream, under the session's workspace.  keep_state: the session's
+        per-request state is put back afterwards -- a graph only reads device memory, so it must not see the
+        prefill-time counter values (capture does not execute kernels on ROCm/CUDA; restored anyway for safety)."""
+        state = (s.ctr, s.seen, s.finished, s.codes, s.tok0, s.seed) if keep_state else ()
+        snap = [z.clone() for z in state]
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         g = torch.cuda.CUDAGraph()
         with torch.cuda.stream(side), K.use_workspace(s.ws), K.capturing():
             with torch.cuda.graph(g, stream=side):
-                self._frame(s, part)
+                fn()
         torch.cuda.current_stream().wait_stream(side)
-        # capture does not execute kernels on ROCm/CUDA; restore anyway for safety
-        s.ctr.copy_(snap[0]); s.seen.copy_(snap[1]); s.finished.copy_(snap[2]); s.codes.copy_(snap[3])
-        s.tok0.copy_(snap[4]); s.seed.copy_(snap[5])
+        for z, c in zip(state, snap):
+            z.copy_(c)
         return g

@@ -6,7 +6,8 @@
    an fp64 recomputation from the stored operands, printed);
 4. the first packet needs the head's one text token; 5. a starved loop hands out all audio that exists, then raises
    and leaves nothing held; 6. rows that all reached end-of-speech end the stream although their text never closed;
-7. the combinations that are not served are refused on the first next(); 8. stream() without a feed is untouched.
+7. the combinations that are not served are refused on the first next(); 8. stream() without a feed is untouched;
+9. frames are issued and chunks handed out in one literal order, with a feed and without.
 
 Every feed has a timeout of at most 5 s and the one producer thread is joined with a timeout, so a bug ends as a
 failure, not as a stalled process; the starvation cases use timeout=0, which returns at once.
@@ -509,6 +510,66 @@ def test_stream_without_a_feed_is_untouched(models, dtype):
     assert all(torch.equal(a, b) and a.shape[0] >= 1 for a, b in zip(before[0], after[0]))
     for a, b in zip(before[1], after[1]):
         assert a.shape == b.shape and np.array_equal(a.view(np.int32), b.view(np.int32))
+    _nothing_held(model, tok)
+
+
+# ------------------------------------------------------------------------------------------ 9. the order of issue
+def _a(lo, hi):
+    return [("all", k) for k in range(lo, hi + 1)]
+
+
+# decode_iter's contract for max_new_tokens=12 (11 frames), chunk_frames=4, growing chunks: the interval starts at
+# max(first - 1, 1) = 1 and doubles to 2 and then 4; frame 11 is the cap, so it is handed out by the final yield alone
+SCHEDULES = {
+    1: [("cp", 1), ("yield", 1), ("talk", 1)] + _a(2, 3) + [("yield", 3)] + _a(4, 7) + [("yield", 7)] + _a(8, 11)
+       + [("yield", 11)],
+    2: _a(1, 2) + [("yield", 2)] + _a(3, 4) + [("yield", 4)] + _a(5, 8) + [("yield", 8)] + _a(9, 11) + [("yield", 11)],
+}
+
+
+@pytest.mark.parametrize("first", [1, 2])
+def test_frame_schedule_is_the_same_with_and_without_a_gate(models, first, monkeypatch):
+    """The order in which stream() issues frame replays and hands out chunks, plain and with a feed that holds the
+    whole text from the start: ("cp" | "talk" | "all", key bound - prompt length) per _run_frame call, ("yield", frames
+    heard so far) per report.  Both equal the literal schedule."""
+    import qwen_tts.talker as T
+    from cases import make_inputs, talker_cases
+    cfg, _, ms, tok = models
+    model = ms["fp32"]
+    case = talker_cases()["cv_b3_auto_nospk"]
+    ids, _, _, _ = make_inputs(case, 2, cfg["talker_config"]["hidden_size"])
+    rows = [i[0].tolist() for i in ids]
+    kw = dict(languages=case["languages"], speakers=case["speakers"], first_chunk_frames=first, chunk_frames=4,
+              max_new_tokens=12, ignore_eos=True, do_sample=False, subtalker_dosample=False)
+    trace = []
+    orig = T.TalkerEngine._run_frame
+
+    def run_frame(self, s, keys, use_graph=True, part="all"):
+        trace.append((part, keys - s.P))
+        orig(self, s, keys, use_graph, part)
+    monkeypatch.setattr(T.TalkerEngine, "_run_frame", run_frame)
+
+    def run(it):
+        del trace[:]
+        col = _Collect(3)
+        for b, pcm, last in it:
+            col.add(b, pcm, last)
+            ev = ("yield", col.heard(b))
+            if trace[-1] != ev:  # one report hands a chunk to every row
+                trace.append(ev)
+        col.complete()
+        return list(trace)
+
+    plain = run(model.stream(input_ids=ids, non_streaming_mode=False, **kw))
+    feed = _feed(3, 5.0)
+    for b, r in enumerate(rows):
+        feed.push(r[4:-5], row=b)
+        feed.close(row=b)
+    fed = run(_stream(model, [r[:4] for r in rows], feed, **kw))
+    print("plain", plain)
+    print("fed  ", fed)
+    assert plain == fed
+    assert plain == SCHEDULES[first]
     _nothing_held(model, tok)
 
 

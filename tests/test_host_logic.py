@@ -1,6 +1,6 @@
 """Host-side scheduling logic that needs no GPU: the streaming codec's per-row decode windows (voice-clone reference
-prefixes + generated codes + zero padding, qwen_tts.model.TTSModel._stream_window) and the data-parallel shard
-assignment."""
+prefixes + generated codes + zero padding, qwen_tts.model.TTSModel._stream_window), the data-parallel shard
+assignment and the slot table of continuous batching (qwen_tts.talker.SlotTable)."""
 import os
 import sys
 
@@ -51,6 +51,46 @@ def test_shard_longest_first_balances_frames():
     assert sorted(i for s in shards for i in s) == list(range(len(lengths)))
     loads = [sum(lengths[i] for i in s) for s in shards]
     assert max(loads) - min(loads) <= max(lengths)
+
+
+def test_slot_table_refills_first_in_first_out():
+    """The host bookkeeping serve() and serve_iter() share: four requests through two rows."""
+    from qwen_tts.talker import SlotTable
+    tab = SlotTable([5, 9, 3, 7], [None, 4, None, 2], slots=2, max_frames=10)
+    assert (tab.B, tab.P, tab.req, tab.slot_p, list(tab.queue)) == (2, 9, [0, 1], [9, 9], [2, 3])
+    assert tab.cap == [10, 4, 10, 2]
+    assert tab.busy() == [0, 1] and tab.keys() == 10  # the padded prompt + frame 0's own key
+    for _ in range(4):
+        assert not tab.capped(0) and not tab.capped(1)
+        tab.frame += 1
+    assert tab.capped(1) and not tab.capped(0) and tab.frames(1) == 4 and tab.frames(0) == 4
+    assert tab.retire(1) == 2
+    assert (tab.req, tab.start, tab.slot_p, list(tab.queue)) == ([0, 2], [0, 4], [9, 3], [3])
+    assert tab.keys() == max(9 + 4 + 1, 3 + 0 + 1) == 14
+    tab.frame += 2
+    assert tab.keys() == max(9 + 6 + 1, 3 + 2 + 1) and tab.frames(1) == 2
+    assert tab.retire(0) == 3 and tab.req == [3, 2] and not tab.queue  # (say request 0 ended on its EOS)
+    assert tab.keys() == max(7 + 0 + 1, 3 + 2 + 1)
+    tab.frame += 2
+    assert tab.capped(0) and tab.frames(0) == 2
+    tab.frame += 1
+    assert tab.frames(0) == 2  # never past the cap, however late the row is retired
+    assert tab.retire(0) == -1 and tab.req == [-1, 2]
+    assert tab.busy() == [1] and tab.keys() == 3 + 5 + 1  # an idle row leaves the busy list and the bound
+    assert tab.retire(1) == -1 and tab.busy() == []
+
+
+def test_slot_table_edges_and_empty_serve():
+    from qwen_tts.talker import GenParams, SlotTable, TalkerEngine
+    tab = SlotTable([4, 6, 5], [None, None, None], slots=8, max_frames=3)  # more rows than requests: B = n
+    assert (tab.B, tab.req, tab.slot_p, list(tab.queue)) == (3, [0, 1, 2], [6, 6, 6], [])
+    tab = SlotTable([], [], slots=8, max_frames=3)
+    assert tab.B == 0 and tab.busy() == [] and not tab.queue
+    # no requests: serve() and serve_iter() end at once and take no session (an engine with no state at all suffices)
+    eng = object.__new__(TalkerEngine)
+    assert list(eng.serve([], None, GenParams())) == []
+    assert list(eng.serve_iter([], None, GenParams())) == []
+    assert vars(eng) == {}
 
 
 def test_bench_module_helpers():
