@@ -120,6 +120,20 @@ class SampleArgs(ctypes.Structure):
                 ("pick", c_void_p), ("rows", c_void_p)]
 
 
+PCM_F32, PCM_S16 = 0, 1  # QT_PCM_*
+
+
+class ResampleRow(ctypes.Structure):
+    """qt_resample_row: one row of a qt_resample call (host table)"""
+    _fields_ = [("src", c_void_p), ("out", c_void_p), ("hist_in", c_void_p), ("hist_out", c_void_p), ("pos", c_ll),
+                ("m0", c_ll), ("n", c_int), ("count", c_int), ("flush", c_int), ("reserved", c_int)]
+
+
+class ResampleArgs(ctypes.Structure):
+    _fields_ = [("up", c_int), ("down", c_int), ("half", c_int), ("taps", c_int), ("H", c_int), ("format", c_int),
+                ("B", c_int), ("reserved", c_int), ("table", c_void_p), ("rows", ctypes.POINTER(ResampleRow))]
+
+
 EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decode_attention", "qt_decode_attn_ws_bytes",
            "qt_rmsnorm_rec", "qt_small_prefill_attention",
            "qt_decode_attn_oproj", "qt_attn_oproj_ws_bytes", "qt_attn_oproj_resident_blocks",
@@ -128,7 +142,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_talker_tail_supported",
            "qt_sample", "qt_sample_row_bytes", "qt_sample_args_bytes", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
            "qt_stream_window", "qt_stream_rows", "qt_trail_append",
-           "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm",
+           "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
 
@@ -185,6 +199,7 @@ def load_library(path: str = LIB_PATH):
         "qt_snake": [P, P, c_int, c_ll, c_int, P, P, P],
         "qt_dwconv_ln": [P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, P, P],
         "qt_clamp_pcm": [P, c_int, c_ll, P, P],
+        "qt_resample": [P, P],
         "qt_decode_attn_ws_bytes": [c_int, c_int, c_int, c_int, c_int],
         "qt_decode_attn_oproj": [P, P],
         "qt_attn_oproj_ws_bytes": [c_int, c_int],

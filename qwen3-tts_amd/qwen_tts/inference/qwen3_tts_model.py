@@ -19,6 +19,7 @@ import torch
 
 from .. import audio as _audio
 from .. import kernels as _kernels
+from .. import resample as _resample
 from ..model import TTSModel
 from ..text import load_processor
 from ..speaker import speaker_specs
@@ -196,8 +197,15 @@ class Qwen3TTSModel:
                       max_new_tokens=pick("max_new_tokens", max_new_tokens))
         return merged
 
-    def _decode(self, codes_list):
-        return self.model.speech_tokenizer.decode([{"audio_codes": c} for c in codes_list])
+    def _decode(self, codes_list, sample_rate=None, pcm_format="f32", cut=None):
+        return self.model.speech_tokenizer.decode([{"audio_codes": c} for c in codes_list], sample_rate, pcm_format,
+                                                  _cut=cut)
+
+    def _output_format(self, sample_rate, pcm_format):
+        """Validate the output format before anything runs; returns the rate the caller will get."""
+        tok = self.model.speech_tokenizer
+        fmt = _resample.output_format(sample_rate, pcm_format, tok.get_output_sample_rate())
+        return tok.get_output_sample_rate() if fmt is None else fmt[0].sample_rate
 
     # ---------------------------------------------------------------- voice clone (W:356-633)
     def create_voice_clone_prompt(self, ref_audio, ref_text=None, x_vector_only_mode=False) -> List[VoiceClonePromptItem]:
@@ -254,7 +262,9 @@ class Qwen3TTSModel:
 
     @torch.no_grad()
     def generate_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False,
-                             voice_clone_prompt=None, non_streaming_mode=False, **kwargs):
+                             voice_clone_prompt=None, non_streaming_mode=False, sample_rate=None, pcm_format="f32",
+                             **kwargs):
+        self._output_format(sample_rate, pcm_format)
         input_ids, ref_ids, vcp, languages = self._voice_clone_inputs(text, language, ref_audio, ref_text,
                                                                       x_vector_only_mode, voice_clone_prompt)
         codes, _ = self.model.generate(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp, languages=languages,
@@ -263,6 +273,11 @@ class Qwen3TTSModel:
         refs = vcp.get("ref_code", None)
         dec = [torch.cat([refs[i].cpu().long(), c], 0) if refs is not None and refs[i] is not None else c
                for i, c in enumerate(codes)]
+        if _resample.output_format(sample_rate, pcm_format, self.model.speech_tokenizer.get_output_sample_rate()):
+            # the same cut, taken on the device in front of the resampler
+            return self._decode(dec, sample_rate, pcm_format,
+                                cut=[(int(refs[i].shape[0]), int(d.shape[0])) if refs is not None and refs[i] is not None
+                                     else None for i, d in enumerate(dec)])
         wavs, fs = self._decode(dec)
         out = []
         for i, w in enumerate(wavs):
@@ -276,21 +291,23 @@ class Qwen3TTSModel:
     @torch.no_grad()
     def stream_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False,
                            voice_clone_prompt=None, non_streaming_mode=False, first_chunk_frames=1, chunk_frames=48,
-                           **kwargs):
+                           sample_rate=None, pcm_format="f32", **kwargs):
         """New surface (no reference counterpart, SURVEY.md §8f-1 + 8f-2): streaming voice clone.  Same inputs as
         generate_voice_clone (reference audio is encoded / x-vectored at submit); yields (utterance index, pcm chunk
         np.float32, sample rate, is_last).  Per utterance the chunks concatenate to generate_voice_clone()'s PCM: in
         ICL mode the reference codes are decoded in front of the generated ones and the output starts at their
         boundary -- the wrapper's proportional cut keeps floor(555 R / T) more samples of the reference's tail, a
-        length-dependent point a stream cannot know in advance (TTSModel._stream_stateful)."""
+        length-dependent point a stream cannot know in advance (TTSModel._stream_stateful).  sample_rate /
+        pcm_format: as in stream()."""
+        sr = self._output_format(sample_rate, pcm_format)
         input_ids, ref_ids, vcp, languages = self._voice_clone_inputs(text, language, ref_audio, ref_text,
                                                                       x_vector_only_mode, voice_clone_prompt)
-        sr = self.model.speech_tokenizer.get_output_sample_rate()
         for i, pcm, last in self.model.stream(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp,
                                               languages=languages, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
+                                              sample_rate=sample_rate, pcm_format=pcm_format,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
-            yield i, pcm.to(torch.float32).cpu().numpy(), sr, last
+            yield i, (pcm if pcm.dtype == torch.int16 else pcm.to(torch.float32)).cpu().numpy(), sr, last
 
     def _voice_clone_inputs(self, text, language, ref_audio, ref_text, x_vector_only_mode, voice_clone_prompt):
         """W:460-633 input handling of generate_voice_clone: -> (input_ids, ref_ids, voice_clone_prompt dict,
@@ -332,7 +349,9 @@ class Qwen3TTSModel:
 
     # ---------------------------------------------------------------- voice design (W:637-728)
     @torch.no_grad()
-    def generate_voice_design(self, text, instruct, language=None, non_streaming_mode=True, **kwargs):
+    def generate_voice_design(self, text, instruct, language=None, non_streaming_mode=True, sample_rate=None,
+                              pcm_format="f32", **kwargs):
+        self._output_format(sample_rate, pcm_format)
         if self.model.tts_model_type != "voice_design":
             raise ValueError(f"model with tts_model_type: {self.model.tts_model_type} does not support "
                              "generate_voice_design, Please check Model Card or Readme for more details.")
@@ -353,7 +372,7 @@ class Qwen3TTSModel:
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        non_streaming_mode=non_streaming_mode,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
-        return self._decode(codes)
+        return self._decode(codes, sample_rate, pcm_format)
 
     # ---------------------------------------------------------------- custom voice (W:732-839)
     def _custom_voice_inputs(self, text, speaker, language, instruct):
@@ -384,16 +403,19 @@ class Qwen3TTSModel:
         return input_ids, ins_ids, languages, speakers
 
     @torch.no_grad()
-    def generate_custom_voice(self, text, speaker, language=None, instruct=None, non_streaming_mode=True, **kwargs):
+    def generate_custom_voice(self, text, speaker, language=None, instruct=None, non_streaming_mode=True,
+                              sample_rate=None, pcm_format="f32", **kwargs):
+        self._output_format(sample_rate, pcm_format)
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        speakers=speakers, non_streaming_mode=non_streaming_mode,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
-        return self._decode(codes)
+        return self._decode(codes, sample_rate, pcm_format)
 
     @torch.no_grad()
     def stream(self, text, speaker=None, language=None, instruct=None, non_streaming_mode=None,
-               first_chunk_frames=1, chunk_frames=48, left_context=None, max_batch=None, text_feed=None, **kwargs):
+               first_chunk_frames=1, chunk_frames=48, left_context=None, max_batch=None, text_feed=None,
+               sample_rate=None, pcm_format="f32", **kwargs):
         """New surface (no reference counterpart): streaming custom-voice generation.
         Yields (utterance index, pcm chunk np.float32, sample rate, is_last) while the batch decodes: the first
         chunk arrives after prefill + `first_chunk_frames` decode frames (1 frame: 1365 samples = 57 ms of audio,
@@ -412,20 +434,26 @@ class Qwen3TTSModel:
         utterance's text.  Each piece is tokenized on its own, and piece-wise BPE is not the whole sentence's BPE
         (cut at word boundaries); what is guaranteed is stated on ids: after close, an utterance is decoded exactly
         as the whole id sequence would be in streaming-text mode (non_streaming_mode=False, the only mode here).
-        non_streaming_mode defaults to True as in generate_custom_voice(), and to False with a text_feed."""
+        non_streaming_mode defaults to True as in generate_custom_voice(), and to False with a text_feed.
+
+        sample_rate / pcm_format: the chunks at that rate (8000 .. 48000) as np.float32 or, with "s16",
+        np.int16, resampled on the device by a stateful filter (qwen_tts.PcmResampler): per utterance they concatenate
+        to the resampled whole, ceil(N * rate / 24000) samples for the default's N, whatever the chunking; up to
+        10 * max(1, 24000 / rate) input samples' worth of output waits for the next chunk (the last one flushes)."""
+        sr = self._output_format(sample_rate, pcm_format)
         if non_streaming_mode is None:
             non_streaming_mode = text_feed is None
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
         if text_feed is not None:  # heads: role ids + the first piece, no template suffix
             input_ids = self._tokenize_texts([f"<|im_start|>assistant\n{t}" for t in self._ensure_list(text)])
             text_feed.processor = self.processor
-        sr = self.model.speech_tokenizer.get_output_sample_rate()
         for i, pcm, last in self.model.stream(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                               speakers=speakers, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
                                               left_context=left_context, max_batch=max_batch, text_feed=text_feed,
+                                              sample_rate=sample_rate, pcm_format=pcm_format,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
-            yield i, pcm.to(torch.float32).cpu().numpy(), sr, last
+            yield i, (pcm if pcm.dtype == torch.int16 else pcm.to(torch.float32)).cpu().numpy(), sr, last
 
     def text_feed(self, rows: int = 1, timeout: float = 30.0):
         """A qwen_tts.TextFeed for stream(text_feed=...) whose push_text tokenizes with this model's processor (usable

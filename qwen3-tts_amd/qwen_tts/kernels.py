@@ -523,6 +523,18 @@ def clamp_pcm(x, n, out):
     check(_hip.lib().qt_clamp_pcm(ptr(x), _hip.dtype_code(x.dtype), n, ptr(out), stream()), "qt_clamp_pcm")
 
 
+def resample(table, up, down, half, taps, H, pcm_format, rows):
+    """qt_resample: rows = one (src, out, hist_in, hist_out, pos, m0, n, count, flush) per row, pointers as ints or
+    None (resample.PcmResampler.push builds them and owns the counters)."""
+    tab = (_hip.ResampleRow * len(rows))()
+    for r, (src, out, hin, hout, pos, m0, n, count, flush) in zip(tab, rows):
+        r.src, r.out, r.hist_in, r.hist_out = src, out, hin, hout
+        r.pos, r.m0, r.n, r.count, r.flush = pos, m0, n, count, flush
+    a = _hip.ResampleArgs(up, down, half, taps, H, _hip.PCM_S16 if pcm_format == "s16" else _hip.PCM_F32, len(rows), 0,
+                          ptr(table), tab)
+    check(_hip.lib().qt_resample(ctypes.byref(a), stream()), "qt_resample")
+
+
 def rope_tables(head_dim: int, theta: float, npos: int, device):
     """cos/sin [npos][D/2] computed exactly as the reference (fp32 on CPU, M:526-592), then uploaded."""
     inv = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).to(dtype=torch.float) / head_dim))

@@ -11,6 +11,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import kernels as K
+from .resample import PcmResampler, output_format
 from .talker import MIN_NEW_TOKENS, GenParams, HandoffWatch, TalkerEngine
 
 
@@ -351,7 +352,7 @@ class TTSModel:
                temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
                first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None,
-               text_feed=None, **kwargs):
+               text_feed=None, sample_rate=None, pcm_format="f32", **kwargs):
         """Streaming generation (the reference has none): yields (row, pcm, last) as frames finish.
 
         Per row the chunks concatenate to the one-shot generate() + decode() PCM (Z:259-365): the reference
@@ -376,7 +377,18 @@ class TTSModel:
         first_chunk_frames=1 the first packet needs the first text id alone.  After feed.close(b), row b has decoded
         exactly what a whole-text call with role + text + suffix ids decodes in streaming-text mode.  When the text
         runs out, all audio generated so far is yielded, then the loop waits up to feed.timeout seconds and raises
-        TextFeedTimeout.  Only the thread running this generator issues GPU work; push / close may come from any."""
+        TextFeedTimeout.  Only the thread running this generator issues GPU work; push / close may come from any.
+
+        sample_rate / pcm_format: pcm at that rate, fp32 or ("s16") int16.  Each row's default sample
+        sequence goes through a stateful device resampler (resample.PcmResampler), one launch per codec report for all
+        rows, so the chunks concatenate to the resampled whole -- ceil(N * up / down) samples for the default's N --
+        bit for bit whatever the chunking.  Outputs that need samples not generated yet (at most 10 * max(1, down / up)
+        input samples' worth) follow with the next chunk; last=True flushes, so the last chunk may hold samples where
+        the default's is empty.  The stateless left_context form serves the default format only."""
+        fmt = self._output_format(sample_rate, pcm_format)
+        if fmt is not None and left_context is not None:
+            raise NotImplementedError("stream(left_context=...) with sample_rate / pcm_format: use the default "
+                                      "stateful stream")
         if text_feed is not None:
             yield from self._stream_fed(text_feed, input_ids, instruct_ids, voice_clone_prompt, languages, speakers,
                                         non_streaming_mode, left_context, max_batch, first_chunk_frames, chunk_frames,
@@ -384,7 +396,7 @@ class TTSModel:
                                         GenParams(max_new_tokens, do_sample, top_k, top_p, temperature,
                                                   subtalker_dosample, subtalker_top_k, subtalker_top_p,
                                                   subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos,
-                                                  seed))
+                                                  seed), fmt)
             return
         if max_batch is not None and input_ids is not None and len(input_ids) > int(max_batch):
             if left_context is not None:
@@ -394,7 +406,8 @@ class TTSModel:
                 max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
                 subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed,
                 max_batch=max_batch, first_chunk_frames=first_chunk_frames,
-                chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, **kwargs)
+                chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, sample_rate=sample_rate,
+                pcm_format=pcm_format, **kwargs)
             return
         dec = self.speech_tokenizer.model
         up = dec.total_upsample
@@ -428,7 +441,7 @@ class TTSModel:
         # the generation of the next one (~3 ms per frame), so playback started at the first packet never starves
         if left_context is None:
             yield from self._stream_stateful(dec, emb, mask, trail, pad, gp, B, eos, first_chunk_frames, chunk_frames,
-                                             use_graph, prefix, started)
+                                             use_graph, prefix, started, fmt=fmt)
             return
         if prefix is not None:
             raise NotImplementedError("stream(left_context=...) with voice-clone reference codes (ICL): use the "
@@ -487,7 +500,7 @@ class TTSModel:
                 break
 
     def _stream_fed(self, feed, heads, instruct_ids, voice_clone_prompt, languages, speakers, non_streaming_mode,
-                    left_context, max_batch, first_chunk_frames, chunk_frames, use_graph, gp):
+                    left_context, max_batch, first_chunk_frames, chunk_frames, use_graph, gp, fmt=None):
         """stream(text_feed=feed): the combinations it does not serve are refused before anything is allocated."""
         from .feed import TextFeed
         from .talker import TextGate
@@ -518,7 +531,7 @@ class TTSModel:
         gate = TextGate(feed, [len(h) - 4 for h in heads], self.config["tts_eos_token_id"])
         yield from self._stream_stateful(self.speech_tokenizer.model, emb, mask, trail, pad, gp, B,
                                          self.engine.tc["codec_eos_token_id"], first_chunk_frames, chunk_frames,
-                                         use_graph, gate=gate)
+                                         use_graph, gate=gate, fmt=fmt)
 
     @torch.no_grad()
     def serve_stream(self, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None, languages=None,
@@ -526,7 +539,7 @@ class TTSModel:
                      top_p=1.0, temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                      subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False,
                      seed=None, max_batch=8, first_chunk_frames=1, chunk_frames=8, use_graph=True, philox_ids=None,
-                     frame_caps=None, **kwargs):
+                     frame_caps=None, sample_rate=None, pcm_format="f32", **kwargs):
         """Streaming from the continuously batched route (the reference has neither): the requests are
         decoded through max_batch batch rows as generate(max_batch=...) decodes them, and each request's audio
         leaves as it is generated -- yields (request index, pcm, last).
@@ -539,7 +552,10 @@ class TTSModel:
         others continue, idle ones ride along), so a refilled request has a first packet of its own.  A row that
         reaches the end of a reference chunk restarts on the chunk's 25 context frames (their output discarded)
         while the other rows carry on.  The sampling parameters take per-request lists as in generate().  Voice-clone
-        prompts that carry reference codes (ICL) are not supported here; x-vector-only prompts are."""
+        prompts that carry reference codes (ICL) are not supported here; x-vector-only prompts are.
+        sample_rate / pcm_format: as in stream() -- one resampler launch per codec feed for all slots, a slot's state
+        reset when its request changes."""
+        fmt = self._output_format(sample_rate, pcm_format)
         refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
         if refs is not None and any(r is not None for r in refs):
             raise NotImplementedError("serve_stream() / stream(max_batch=...) with voice-clone reference codes (ICL): "
@@ -560,6 +576,7 @@ class TTSModel:
         caps = sorted({first, every})  # feed capacities (one captured codec graph each)
         dev = self.device
         rs = dec.row_stream(B, RX + RC, caps[-1])
+        out = None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, dev)
         rows_ix = torch.arange(B, device=dev)[:, None]
         req = [-1] * B        # request in each slot, as the codec has seen it
         discard = [0] * B     # samples of the slot's decode still to drop (a restarted chunk's context)
@@ -576,6 +593,8 @@ class TTSModel:
                     i, lo, f, ended[b], nzb = r
                     if req[b] != i:
                         req[b], discard[b], cum[b], nz[b] = i, 0, 0, 0
+                        if out is not None:
+                            out.reset(b)
                     nz[b] += nzb
                     for t in range(lo, f):
                         if t % RC == 0:  # frame t opens a reference chunk: begin, after chunk 0 on the 25 context frames
@@ -584,6 +603,9 @@ class TTSModel:
                             todo[b] += range(t - ctx, t)
                         todo[b].append(t)
                     if ended[b] and not todo[b]:  # nothing new: the request's audio was complete already
+                        if out is not None:  # what the filter still holds back
+                            yield i, out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b], True
+                            continue
                         yield i, torch.zeros(0, device=dev), True
                 at = [0] * B
                 while any(at[b] < len(todo[b]) for b in range(B)):
@@ -597,6 +619,7 @@ class TTSModel:
                     ix = torch.tensor([todo[b][at[b]:at[b] + nrow[b]] + [0] * (n - nrow[b]) for b in range(B)],
                                       dtype=torch.long).pin_memory().to(dev, non_blocking=True)
                     pcm = rs.feed(s.codes[rows_ix, ix], nrow, begin)
+                    pend = []  # (slot, first sample, samples, last) of this feed, for the resampler's one launch
                     for b in range(B):
                         if not nrow[b]:
                             continue
@@ -612,9 +635,33 @@ class TTSModel:
                             hi_s = min(hi_s, lo_s + max(up * nz[b] - cum[b], 0))
                         if hi_s > lo_s or last:
                             cum[b] += hi_s - lo_s
+                            if out is not None:
+                                pend.append((b, lo_s, hi_s - lo_s, last))
+                                continue
                             yield req[b], pcm[b, lo_s:hi_s].clone(), last
+                    if pend:
+                        yield from self._resampled(out, pcm, pend, req)
         finally:
             rs.close()
+
+    def _output_format(self, sample_rate, pcm_format):
+        """The streams' output format, validated before anything is allocated: None = the codec's own (24 kHz fp32,
+        no resampler), else (resample.Plan, pcm_format)."""
+        tok = self.speech_tokenizer
+        return output_format(sample_rate, pcm_format, 24000 if tok is None else tok.get_output_sample_rate())
+
+    @staticmethod
+    def _resampled(out, pcm, pend, names=None):
+        """One resampler launch for the (row, first sample, samples, last) entries of `pend`, samples taken from
+        pcm [B, L]; yields (row or names[row], chunk, last) for the rows that got samples or end."""
+        B = out.rows
+        offs, lens, flush = [0] * B, [0] * B, [False] * B
+        for b, o, n, last in pend:
+            offs[b], lens[b], flush[b] = o, n, last
+        chunks = out.push(pcm, offs, lens, flush)
+        for b, _, _, last in pend:
+            if chunks[b].numel() or last:
+                yield (b if names is None else names[b]), chunks[b], last
 
     @staticmethod
     def _stream_window(codes, pre, R, end, lo, hi):
@@ -657,7 +704,7 @@ class TTSModel:
         return pre, side, cs, fed
 
     def _stream_stateful(self, dec, emb, mask, trail, pad, gp, B, eos, first_chunk_frames, chunk_frames, use_graph,
-                         prefix=None, started=None, gate=None):
+                         prefix=None, started=None, gate=None, fmt=None):
         """stream() on the incremental codec: every final frame is fed once to the decoder of its reference chunk
         and every sample computable from the frames fed so far is emitted -- 1920 n - 555 samples of a chunk after
         its n frames, i.e. no lookahead frame is waited for (the 555 samples that need it follow with the next
@@ -689,6 +736,7 @@ class TTSModel:
         scanned = 0                       # cb0 columns already searched for EOS
         k, cs, fed, emit_s, ctx_s = 0, None, 0, 0, 0   # reference chunk, its decoder, positions fed, samples emitted
         main, side = torch.cuda.current_stream(dev), None
+        out = None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, dev)
         if started is not None:  # stream() began decoding the reference frames before the prompt assembly
             _, side, cs, fed = started
         elif min(R) > 0:
@@ -744,6 +792,7 @@ class TTSModel:
                         fed = hi
                     n = max(cs.ns - ctx_s - emit_s, 0)
                     ended = t_end is not None and fed >= t_end
+                    pend = []  # (row, first sample, samples, last) of this report, for the resampler's one launch
                     for b in range(B):
                         if done[b] or n == 0:
                             continue
@@ -755,10 +804,19 @@ class TTSModel:
                         o = ctx_s + emit_s + (lo_s - gpos)
                         chunk = cs.pcm[b, o:o + max(hi_s - lo_s, 0)]
                         done[b] = last
+                        if out is not None:
+                            pend.append((b, o, max(hi_s - lo_s, 0), last))
+                            continue
                         if unchecked:  # flags copied behind the feed that produced this PCM: the caller waits on it anyway
                             HandoffWatch(sessions).check()
                             unchecked = False
                         yield b, chunk, last
+                    if pend:  # queued directly behind the codec feed, before the hand-off check synchronises
+                        chunks = list(self._resampled(out, cs.pcm, pend))
+                        if unchecked:
+                            HandoffWatch(sessions).check()
+                            unchecked = False
+                        yield from chunks
                     emit_s += n
                     gpos += n
                     if fed == cend and not ended:  # chunk k complete (its 555-sample tail is dropped): next chunk
@@ -773,6 +831,9 @@ class TTSModel:
                                 HandoffWatch(sessions).check()
                                 unchecked = False
                             done[b] = True
+                            if out is not None:  # what the filter still holds back
+                                yield b, out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b], True
+                                continue
                             yield b, torch.zeros(0, device=codes.device), True
                 if all(done):
                     break

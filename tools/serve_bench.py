@@ -15,7 +15,12 @@ Both include prompt assembly and the codec decode of every request.  Prints one 
 `serve`, and every request's audio leaves in chunks while it decodes.  Its line also gives, per request, the time
 from the moment its prefill was queued to its first chunk being complete on the host's side of the stream (p50, p90).
 
+--sample-rate / --pcm select the stream's output format (resampled and converted on the device); the
+defaults are the codec's own 24 kHz fp32.  --ab 16000:s16,48000:f32 runs those formats beside the selected one in the
+same process, alternating within every repetition, one line each; --only-stream skips the first two schedules.
+
     python tools/serve_bench.py [--requests 8] [--slots 8] [--extra-slots 16,32] [--stream]
+        [--sample-rate 16000 --pcm s16] [--ab 16000:s16,48000:f32] [--only-stream]
 """
 from __future__ import annotations
 
@@ -57,6 +62,10 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--stream", action="store_true", help="also run the list through serve_stream")
     ap.add_argument("--chunk-frames", type=int, default=8)
+    ap.add_argument("--sample-rate", type=int, default=None, help="output rate of the stream schedule (default 24000)")
+    ap.add_argument("--pcm", default="f32", choices=["f32", "s16"], help="sample format of the stream schedule")
+    ap.add_argument("--ab", default="", help="more rate:format pairs for the stream schedule, run alternately")
+    ap.add_argument("--only-stream", action="store_true", help="skip the padded and serve schedules")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from qwen_tts import Qwen3TTSModel
@@ -101,13 +110,16 @@ def main():
 
     first_ms = []
 
-    def stream(slots, seed):
+    formats = [(a.sample_rate, a.pcm)] + [(int(x.split(":")[0]), x.split(":")[1]) for x in a.ab.split(",") if x]
+
+    def stream(slots, seed, fmt=formats[0]):
         """serve_stream: returns the samples received per request; first-chunk latencies go to first_ms"""
         got, lat = [0] * len(reqs), {}
+        out = {} if fmt == (None, "f32") else dict(sample_rate=fmt[0], pcm_format=fmt[1])
         it = m.serve_stream(input_ids=[r[0] for r in reqs], instruct_ids=[r[1] for r in reqs],
                             languages=["english"] * len(reqs), non_streaming_mode=True, max_new_tokens=max(F) + 1,
                             seed=seed, frame_caps=F, max_batch=slots, first_chunk_frames=1,
-                            chunk_frames=a.chunk_frames, **gen)
+                            chunk_frames=a.chunk_frames, **gen, **out)
         for i, pcm, last in it:
             if i not in lat:  # the chunk is usable once the stream has produced it
                 torch.cuda.current_stream().synchronize()
@@ -117,18 +129,23 @@ def main():
         return got
 
     def run_stream(slots):
-        stream(slots, 1)  # warmup (graph captures, sessions, codec slot)
-        ts, lats = [], []
+        """{format: (wall times, first-chunk latencies)}; the formats alternate within every repetition"""
+        res = {fmt: ([], []) for fmt in formats}
+        for fmt in formats:
+            stream(slots, 1, fmt)  # warmup (graph captures, sessions, codec slot)
         for r in range(a.reps):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            got = stream(slots, 10 + r)
-            torch.cuda.synchronize()
-            ts.append(time.perf_counter() - t0)
-            lats += first_ms
-            # every frame's 1920 samples but each reference chunk's last 555 (fewer only where a cb0 is 0)
-            assert all(0 < g <= 1920 * f - 555 * -(-f // 300) for g, f in zip(got, F)), got
-        return ts, lats
+            for fmt in formats:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                got = stream(slots, 10 + r, fmt)
+                torch.cuda.synchronize()
+                res[fmt][0].append(time.perf_counter() - t0)
+                res[fmt][1].extend(first_ms)
+                # every frame's 1920 samples but each reference chunk's last 555 (fewer only where a cb0 is 0), at
+                # the output rate
+                rate = 24000 if fmt[0] is None else fmt[0]
+                assert all(0 < g <= -(-(1920 * f - 555 * -(-f // 300)) * rate // 24000) for g, f in zip(got, F)), got
+        return res
 
     def run(fn, slots):
         fn(slots, 1)  # warmup (graph capture, sessions)
@@ -144,7 +161,7 @@ def main():
         return ts
 
     slot_list = [a.slots] + [int(x) for x in a.extra_slots.split(",") if x]
-    for name, fn in (("padded", padded), ("serve", serve)):
+    for name, fn in (() if a.only_stream else (("padded", padded), ("serve", serve))):
         for slots in slot_list:
             if name == "padded" and slots != a.slots:
                 continue
@@ -160,11 +177,11 @@ def main():
                                           "F U[64,320], sampling, ignore_eos + per-request cap, + codec decode"}),
                   flush=True)
     if a.stream:
-        for slots in slot_list:
-            ts, lats = run_stream(slots)
+        for slots, (fmt, (ts, lats)) in ((s, kv) for s in slot_list for kv in run_stream(s).items()):
             dt = float(np.median(ts))
             st = getattr(eng, "serve_stats", {})
             print(json.dumps({"schedule": "serve_stream", "slots": slots, "requests": a.requests,
+                              "sample_rate": 24000 if fmt[0] is None else fmt[0], "pcm": fmt[1],
                               "chunk_frames": a.chunk_frames, "frames_replayed": st.get("frames"),
                               "frames_min": -(-sum(F) // slots), "audio_s": round(audio_s, 2),
                               "wall_s": round(dt, 4), "audio_s_per_s": round(audio_s / dt, 2),
