@@ -99,6 +99,13 @@ class TalkerTailArgs(ctypes.Structure):
                 ("qkv", c_void_p), ("ldq", c_ll), ("ws", c_void_p), ("ws_bytes", c_ll), ("H", c_int), ("I", c_int)]
 
 
+class CodecResunitArgs(ctypes.Structure):
+    _fields_ = [("B", c_int), ("L", c_int), ("C", c_int), ("dil", c_int), ("a_dtype", c_int), ("w_dtype", c_int),
+                ("x_in", c_void_p), ("x_out", c_void_p),
+                ("w1", c_void_p), ("b1", c_void_p), ("s1_alpha", c_void_p), ("s1_inv_beta", c_void_p),
+                ("w2", c_void_p), ("b2", c_void_p), ("s2_alpha", c_void_p), ("s2_inv_beta", c_void_p)]
+
+
 class SampleRow(ctypes.Structure):
     """qt_sample_row: one row's sampling parameters (32 bytes; records of a device table, SampleArgs.rows)"""
     _fields_ = [("temperature", c_float), ("top_p", c_float), ("rep_penalty", c_float), ("top_k", c_int),
@@ -139,7 +146,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_decode_attn_oproj", "qt_attn_oproj_ws_bytes", "qt_attn_oproj_resident_blocks",
            "qt_cp_step", "qt_cp_prefill", "qt_cp_step_sampled", "qt_cp_step_ws_bytes", "qt_cp_step_supported", "qt_cp_step_dbg_bytes",
            "qt_talker_tail", "qt_talker_tail_ws_bytes", "qt_talker_tail_stamp_bytes", "qt_talker_tail_dbg_bytes",
-           "qt_talker_tail_supported",
+           "qt_talker_tail_supported", "qt_codec_resunit", "qt_codec_resunit_supported",
            "qt_sample", "qt_sample_row_bytes", "qt_sample_args_bytes", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
            "qt_stream_window", "qt_stream_rows", "qt_trail_append",
            "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample",
@@ -208,6 +215,7 @@ def load_library(path: str = LIB_PATH):
         "qt_cp_step_supported": [c_int, c_int, c_int, c_int, c_int, c_int, c_int],
         "qt_talker_tail": [P, P], "qt_talker_tail_ws_bytes": [], "qt_talker_tail_stamp_bytes": [], "qt_talker_tail_dbg_bytes": [],
         "qt_talker_tail_supported": [c_int, c_int, c_int, c_int, c_int],
+        "qt_codec_resunit": [P, P], "qt_codec_resunit_supported": [P],
         "qt_pad_time": [P, c_ll, P, c_ll, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_ll, P],
         "qt_zero_tail": [P, c_int, c_int, c_int, c_int, c_int, c_ll, P],
         "qt_layernorm": [P, c_ll, P, P, c_float, P, c_int, c_ll, c_int, c_int, P],

@@ -25,9 +25,13 @@ def _w(W, name, dev):
 
 
 class CodecDecoder:
-    def __init__(self, ccfg: dict, weights: Dict[str, torch.Tensor], dtype="bf16", device="cuda"):
+    def __init__(self, ccfg: dict, weights: Dict[str, torch.Tensor], dtype="bf16", device="cuda", fuse_units=True):
         _hip.lib()
         self.ccfg = ccfg
+        # forward(): a residual unit of the 96 / 192-channel blocks runs as one qt_codec_resunit launch (same bits)
+        # instead of two qt_gemm calls; off = the two-call route everywhere (the A/B and its equality test)
+        self.fuse_units = fuse_units
+        self._unit_fused = {}  # (C, dil, B, L, workspace?) -> does forward() take the one-launch unit
         self.d = d = ccfg["decoder_config"]
         self.dev = dev = torch.device(device)
         self.wdt = wdt = torch.bfloat16 if dtype == "bf16" else torch.float32
@@ -116,6 +120,24 @@ class CodecDecoder:
         dil = getattr(Wt, "dil", 1)
         self._conv(x, Wt, B, T, T, -(Wt.taps - 1) * dil, out, cin, epi, snake=snake)
 
+    def _fuses(self, un, x, bb, B, L, C) -> bool:
+        """Does forward() run this residual unit as one qt_codec_resunit launch: the kernel has the shape, the decoder
+        is bf16, and the unit's k = 7 conv goes the implicit-GEMM route today (a short window that goes through
+        im2col keeps that route and its bits)."""
+        if not self.fuse_units or self.adt != torch.bfloat16:
+            return False
+        key = (C, un["dil"], B, L, K.active_workspace(self.dev) is not None)  # (im2col needs the workspace)
+        hit = self._unit_fused.get(key)
+        if hit is None:
+            hit = K.codec_resunit_supported(x, bb, B, L, C, un["c1"], un["s1"], un["c2"], un["s2"])
+            if hit:
+                c1 = un["c1"]
+                info = K.gemm_route(x, c1, bb, B * L, C, c1.N, conv=(L, L, -(c1.taps - 1) * un["dil"], un["dil"]),
+                                    snake=un["s1"])
+                hit = info.route == _hip.ROUTE_IGEMM
+            self._unit_fused[key] = hit
+        return hit
+
     def _transformer(self, h, B, T):
         """C3 (K:500-574).  h: [B*T][lat] (adt) -> [B*T][lat] (adt)."""
         dev, R = self.dev, B * T
@@ -194,6 +216,11 @@ class CodecDecoder:
             L, C, x = Lo, cout, y
             bb = torch.empty_like(x)
             for un in blk["units"]:
+                if self._fuses(un, x, bb, B, L, C):
+                    # x_out is a second buffer (tiles read their neighbours' x rows): x and bb swap roles per unit
+                    K.codec_resunit(x, bb, B, L, C, un["c1"], un["s1"], un["c2"], un["s2"])
+                    x, bb = bb, x
+                    continue
                 self._causal(x, un["c1"], B, L, bb, C, snake=un["s1"])
                 self._causal(bb, un["c2"], B, L, x, C, epi=_hip.EPI_ADD, snake=un["s2"])
         # C7

@@ -386,6 +386,41 @@ def talker_tail(att, x, R, layer, next_layer, qkv, eps, ws):
     check(_hip.lib().qt_talker_tail(ctypes.byref(a), stream()), "qt_talker_tail")
 
 
+def _codec_resunit_args(x_in, x_out, B, L, C, c1: Tiled, s1, c2: Tiled, s2, dil=None):
+    """The qt_codec_resunit_args of a codec_resunit() / codec_resunit_supported() call (same parameters)."""
+    a = _hip.CodecResunitArgs()
+    a.B, a.L, a.C, a.dil = B, L, C, getattr(c1, "dil", 1) if dil is None else dil
+    a.a_dtype, a.w_dtype = _hip.dtype_code(x_in.dtype), _hip.dtype_code(c1.dtype)
+    a.x_in, a.x_out = ptr(x_in), ptr(x_out)
+    a.w1, a.b1, a.s1_alpha, a.s1_inv_beta = ptr(c1.w), ptr(c1.bias), ptr(s1[0]), ptr(s1[1])
+    a.w2, a.b2, a.s2_alpha, a.s2_inv_beta = ptr(c2.w), ptr(c2.bias), ptr(s2[0]), ptr(s2[1])
+    return a
+
+
+def _is_resunit(C, c1: Tiled, c2: Tiled) -> bool:
+    return (c1.taps, c1.cin, c1.cin_pad, c1.N, c2.taps, c2.cin, c2.cin_pad, c2.N) == (7, C, C, C, 1, C, C, C) \
+        and c2.dtype == c1.dtype
+
+
+def codec_resunit_supported(x_in, x_out, B, L, C, c1: Tiled, s1, c2: Tiled, s2, dil=None) -> bool:
+    """qt_codec_resunit_supported: would codec_resunit() run these arguments (nothing is launched)."""
+    if not _is_resunit(C, c1, c2) or x_out.dtype != x_in.dtype:
+        return False
+    a = _codec_resunit_args(x_in, x_out, B, L, C, c1, s1, c2, s2, dil)
+    return bool(_hip.lib().qt_codec_resunit_supported(ctypes.byref(a)))
+
+
+def codec_resunit(x_in, x_out, B, L, C, c1: Tiled, s1, c2: Tiled, s2, dil=None):
+    """qt_codec_resunit: x_out = x_in + conv2(snake2(conv1(snake1(x_in)))) for one residual unit of the codec decoder in
+    one launch, bit-identical to gemm(c1, snake=s1) into a scratch followed by gemm(c2, snake=s2, epi=EPI_ADD).
+    x_in / x_out: distinct bf16 [B*L][C] tensors; c1 / c2: tile_conv() of the k = 7 dilated and the k = 1 conv (C -> C);
+    s1 / s2: (alpha, 1 / beta) fp32 [C]."""
+    if not _is_resunit(C, c1, c2) or x_out.dtype != x_in.dtype:
+        raise ValueError("codec_resunit: c1 / c2 are not a C -> C residual unit's k = 7 and k = 1 convs")
+    a = _codec_resunit_args(x_in, x_out, B, L, C, c1, s1, c2, s2, dil)
+    check(_hip.lib().qt_codec_resunit(ctypes.byref(a), stream()), "qt_codec_resunit")
+
+
 def sample(logits, R, V, ld, tok_out, *, seen=None, rep_penalty=1.0, n_generated=None, min_new_tokens=0, eos_id=-1,
            suppress=(0, 0, -1), ignore_eos=False, finished=None, do_sample=False, top_k=0, top_p=1.0,
            temperature=1.0, seed=0, step=None, substep=0, codes=None, codes_ld=0, codes_w=16, codes_col=0,
