@@ -141,6 +141,14 @@ class ResampleArgs(ctypes.Structure):
                 ("B", c_int), ("reserved", c_int), ("table", c_void_p), ("rows", ctypes.POINTER(ResampleRow))]
 
 
+KV_ADOPT, KV_EXPORT = 0, 1  # QT_KV_*
+
+
+class KvPrefixJob(ctypes.Structure):
+    """qt_kv_prefix_job: one span of a qt_kv_prefix call"""
+    _fields_ = [("block", c_void_p), ("row", c_int), ("pos", c_int), ("n", c_int), ("dir", c_int)]
+
+
 EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decode_attention", "qt_decode_attn_ws_bytes",
            "qt_rmsnorm_rec", "qt_small_prefill_attention",
            "qt_decode_attn_oproj", "qt_attn_oproj_ws_bytes", "qt_attn_oproj_resident_blocks",
@@ -148,7 +156,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_talker_tail", "qt_talker_tail_ws_bytes", "qt_talker_tail_stamp_bytes", "qt_talker_tail_dbg_bytes",
            "qt_talker_tail_supported", "qt_codec_resunit", "qt_codec_resunit_supported",
            "qt_sample", "qt_sample_row_bytes", "qt_sample_args_bytes", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
-           "qt_stream_window", "qt_stream_rows", "qt_trail_append",
+           "qt_stream_window", "qt_stream_rows", "qt_trail_append", "qt_kv_prefix",
            "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
@@ -200,6 +208,7 @@ def load_library(path: str = LIB_PATH):
         "qt_advance": [P, c_int, P],
         "qt_advance_rows": [P, c_int, c_int, c_int, P],
         "qt_trail_append": [P, P, P, c_int, c_int, c_int, c_int, P],
+        "qt_kv_prefix": [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
         "qt_stream_window": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
         "qt_stream_rows": [P, P, c_int, c_int, P, P, P],
         "qt_rvq_gather": [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P],

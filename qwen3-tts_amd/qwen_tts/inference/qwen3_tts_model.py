@@ -350,7 +350,9 @@ class Qwen3TTSModel:
     # ---------------------------------------------------------------- voice design (W:637-728)
     @torch.no_grad()
     def generate_voice_design(self, text, instruct, language=None, non_streaming_mode=True, sample_rate=None,
-                              pcm_format="f32", **kwargs):
+                              pcm_format="f32", prefix_cache=None, **kwargs):
+        """prefix_cache (not in the reference): a qwen_tts.PrefixCache that keeps each instruction's talker K/V across
+        calls (TTSModel.generate)."""
         self._output_format(sample_rate, pcm_format)
         if self.model.tts_model_type != "voice_design":
             raise ValueError(f"model with tts_model_type: {self.model.tts_model_type} does not support "
@@ -370,7 +372,7 @@ class Qwen3TTSModel:
         input_ids = self._tokenize_texts([self._build_assistant_text(t) for t in texts])
         ins_ids = [None if not x else self._tokenize_texts([self._build_instruct_text(x)])[0] for x in instructs]
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
-                                       non_streaming_mode=non_streaming_mode,
+                                       non_streaming_mode=non_streaming_mode, prefix_cache=prefix_cache,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
         return self._decode(codes, sample_rate, pcm_format)
 
@@ -404,18 +406,21 @@ class Qwen3TTSModel:
 
     @torch.no_grad()
     def generate_custom_voice(self, text, speaker, language=None, instruct=None, non_streaming_mode=True,
-                              sample_rate=None, pcm_format="f32", **kwargs):
+                              sample_rate=None, pcm_format="f32", prefix_cache=None, **kwargs):
+        """prefix_cache (not in the reference): as in generate_voice_design; the 0.6B models drop the instruction
+        (W:799), so their requests leave the cache untouched."""
         self._output_format(sample_rate, pcm_format)
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        speakers=speakers, non_streaming_mode=non_streaming_mode,
+                                       prefix_cache=prefix_cache,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
         return self._decode(codes, sample_rate, pcm_format)
 
     @torch.no_grad()
     def stream(self, text, speaker=None, language=None, instruct=None, non_streaming_mode=None,
                first_chunk_frames=1, chunk_frames=48, left_context=None, max_batch=None, text_feed=None,
-               sample_rate=None, pcm_format="f32", **kwargs):
+               sample_rate=None, pcm_format="f32", prefix_cache=None, **kwargs):
         """New surface (no reference counterpart): streaming custom-voice generation.
         Yields (utterance index, pcm chunk np.float32, sample rate, is_last) while the batch decodes: the first
         chunk arrives after prefill + `first_chunk_frames` decode frames (1 frame: 1365 samples = 57 ms of audio,
@@ -439,7 +444,10 @@ class Qwen3TTSModel:
         sample_rate / pcm_format: the chunks at that rate (8000 .. 48000) as np.float32 or, with "s16",
         np.int16, resampled on the device by a stateful filter (qwen_tts.PcmResampler): per utterance they concatenate
         to the resampled whole, ceil(N * rate / 24000) samples for the default's N, whatever the chunking; up to
-        10 * max(1, 24000 / rate) input samples' worth of output waits for the next chunk (the last one flushes)."""
+        10 * max(1, 24000 / rate) input samples' worth of output waits for the next chunk (the last one flushes).
+
+        prefix_cache: a qwen_tts.PrefixCache -- an utterance whose instruction is cached skips that part of its
+        prefill (TTSModel.generate)."""
         sr = self._output_format(sample_rate, pcm_format)
         if non_streaming_mode is None:
             non_streaming_mode = text_feed is None
@@ -452,6 +460,7 @@ class Qwen3TTSModel:
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
                                               left_context=left_context, max_batch=max_batch, text_feed=text_feed,
                                               sample_rate=sample_rate, pcm_format=pcm_format,
+                                              prefix_cache=prefix_cache,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, (pcm if pcm.dtype == torch.int16 else pcm.to(torch.float32)).cpu().numpy(), sr, last
 

@@ -527,6 +527,38 @@ def trail_append(rows, slots, trailing, n):
     check(_hip.lib().qt_trail_append(ptr(rows), ptr(slots), ptr(trailing), B, T, H, n, stream()), "qt_trail_append")
 
 
+def kv_layer_table(kv):
+    """The 2 * n_layers cache pointers of a session's K/V (kv = (K layers, V layers), each [B][Hkv][Lmax][D]) as a
+    device int64 table, K layers first: qt_kv_prefix's `layers`.  Uploaded from pinned memory, in stream order."""
+    ptrs = [t.data_ptr() for t in kv[0]] + [t.data_ptr() for t in kv[1]]
+    return torch.tensor(ptrs, dtype=torch.int64).pin_memory().to(kv[0][0].device, non_blocking=True)
+
+
+def kv_prefix(jobs, layers, kv):
+    """One qt_kv_prefix launch for jobs = [(block, row, pos, n, dir)]: dir _hip.KV_ADOPT copies the entry block
+    [2][n_layers][Hkv][n][D] into row `row` of every layer's cache from position `pos`, _hip.KV_EXPORT the other way.
+    layers: kv_layer_table(kv).  The job table goes up from pinned memory in stream order; the library checks the
+    host copy (spans inside [0, Lmax), blocks present) before anything is launched."""
+    n_layers = len(kv[0])
+    B, Hkv, Lmax, D = kv[0][0].shape
+    J = len(jobs)
+    if J == 0:
+        return
+    size = ctypes.sizeof(_hip.KvPrefixJob)
+    host = torch.empty(J * size, dtype=torch.uint8).pin_memory()
+    tab = (_hip.KvPrefixJob * J).from_address(host.data_ptr())
+    for j, (block, row, pos, n, d) in enumerate(jobs):
+        if block is not None and (block.dtype != kv[0][0].dtype or block.numel() != 2 * n_layers * Hkv * int(n) * D
+                                  or not block.is_contiguous()):
+            raise ValueError(f"kv_prefix job {j}: the block is not a contiguous [2][{n_layers}][{Hkv}][{n}][{D}] "
+                             f"{kv[0][0].dtype} tensor")
+        tab[j] = _hip.KvPrefixJob(ptr(block), int(row), int(pos), int(n), int(d))
+    dev = torch.empty(J * size, dtype=torch.uint8, device=kv[0][0].device)
+    dev.copy_(host, non_blocking=True)
+    check(_hip.lib().qt_kv_prefix(host.data_ptr(), ptr(dev), J, ptr(layers), n_layers, B, Hkv, Lmax, D,
+                                  _hip.dtype_code(kv[0][0].dtype), stream()), "qt_kv_prefix")
+
+
 def stream_window(hist, x, xin, B, H, n, C, rows_per_frame, head, rows):
     """xin [B][H+n][C] = [hist | x] per the row table rows [2][B] (nrow, begin), then hist = xin[:, m_b:m_b + H]
     (m_b = nrow[b] * rows_per_frame); a beginning row reads zero history and zeros for its first `head` rows."""

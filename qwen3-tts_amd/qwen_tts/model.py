@@ -11,6 +11,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import kernels as K
+from .prefix import PrefixCache, PrefixPlan
 from .resample import PcmResampler, output_format
 from .talker import MIN_NEW_TOKENS, GenParams, HandoffWatch, TalkerEngine
 
@@ -114,14 +115,16 @@ class TTSModel:
         return text + codec, pad_e
 
     def build_prompts(self, input_ids, languages, speakers=None, instruct_ids=None, non_streaming_mode=False,
-                      voice_clone_prompt=None, ref_ids=None, open_text=False):
+                      voice_clone_prompt=None, ref_ids=None, open_text=False, lens_out=None):
         """(embeds [B,P,H] fp32, mask [B,P], trailing [B,T,H], tts_pad [1,1,H]) -- M:2068-2269.
         open_text (streaming-text input; not in the reference): the ids are a request's head -- the three
         role ids and the text known so far, no template suffix -- so every id after the fourth goes to the trailing
         rows and no end-of-text position follows them (the text is not complete; stream(text_feed=...) appends it).
         Two passes: the rows' text-id and codec-id runs are collected on the host first, then projected in one
         text_projection and one codec-embedding gather for the whole batch (one host->device copy each instead of
-        a few per row: the per-row calls were host-bound, ~3.3 ms at B=8), and each row is assembled from slices."""
+        a few per row: the per-row calls were host-bound, ~3.3 ms at B=8), and each row is assembled from slices.
+        lens_out: a list that receives every row's prompt length (the prefix-cache path needs them on the host and
+        would otherwise synchronise on the mask)."""
         e, t, cfg = self.engine, self.tc, self.config
         B = len(input_ids)
         if open_text and non_streaming_mode:
@@ -186,7 +189,7 @@ class TTSModel:
             plans.append(pl)
         runs.run(e)
         if not any(pl["icl"] for pl in plans):
-            return self._assemble_indexed(runs, plans, h_ins, h_special, non_streaming_mode, open_text)
+            return self._assemble_indexed(runs, plans, h_ins, h_special, non_streaming_mode, open_text, lens_out)
         special = runs.get(h_special)[0]
         bos_e, eos_e, pad_e = special[0].view(1, 1, -1), special[1].view(1, 1, -1), special[2].view(1, 1, -1)
         per: List[list] = [[] if h_ins[i] is None else [runs.get(h_ins[i])] for i in range(B)]
@@ -217,6 +220,8 @@ class TTSModel:
             per[i].append(emb)
             trailing.append(trail)
         seqs = [torch.cat(p, 1)[0] for p in per]
+        if lens_out is not None:
+            lens_out[:] = [int(s.shape[0]) for s in seqs]
         P = max(s.shape[0] for s in seqs)
         H = seqs[0].shape[1]
         embeds = torch.zeros(B, P, H, device=self.device)
@@ -230,7 +235,7 @@ class TTSModel:
             trail[i, :tr.shape[1]] = tr[0]
         return embeds, mask, trail, pad_e
 
-    def _assemble_indexed(self, runs, plans, h_ins, h_special, non_streaming_mode, open_text=False):
+    def _assemble_indexed(self, runs, plans, h_ins, h_special, non_streaming_mode, open_text=False, lens_out=None):
         """build_prompts' assembly for non-ICL rows as one gather: every prompt / trailing position is the sum of at
         most two rows of [text projections; codec embeddings; x-vectors; zero row], so the host writes a [positions,
         2] index table and three GPU ops build the whole batch (the per-row slicing / cat / add chain was ~120
@@ -273,6 +278,8 @@ class TTSModel:
                 trails.append([(t(pl["trail"], j), Z) for j in range(pl["trail"][2])] +
                               [(pad if open_text else eos, Z)])
             seqs.append(pos)
+        if lens_out is not None:
+            lens_out[:] = [len(s) for s in seqs]
         P, T = max(len(s) for s in seqs), max(len(tr) for tr in trails)
         idx = [[(Z, Z)] * (P - len(s)) + s for s in seqs] + [tr + [(pad, Z)] * (T - len(tr)) for tr in trails]
         H = (out_t if out_t is not None else out_c).shape[1]
@@ -289,13 +296,37 @@ class TTSModel:
         pad_e = table[pad].view(1, 1, H)
         return embeds, mask, trail, pad_e
 
+    # -------------------------------------------------------------------------------- prefix cache
+    def _prefix_bind(self, prefix_cache):
+        """Check a call's prefix_cache= before anything is allocated; returns the list that build_prompts fills with
+        the prompt lengths (None without a cache)."""
+        if prefix_cache is None:
+            return None
+        if not isinstance(prefix_cache, PrefixCache):
+            raise ValueError(f"prefix_cache must be a qwen_tts.PrefixCache, got {type(prefix_cache).__name__}")
+        prefix_cache.bind(self.engine)
+        return []
+
+    @staticmethod
+    def _prefix_plan(prefix_cache, instruct_ids, voice_clone_prompt, lens):
+        """The engine's view of a call's cache use: request i's key is its instruction's ids.  Requests without an
+        instruction, and every request of a voice-clone call (ICL or x-vector prompts), do not take part."""
+        if prefix_cache is None:
+            return None
+        keys = [None] * len(lens)
+        if instruct_ids is not None and voice_clone_prompt is None:
+            keys = [None if ins is None else (PrefixCache.key(ins) or None) for ins in instruct_ids]
+        if all(k is None for k in keys):
+            return None  # nobody takes part: the call runs exactly the code it runs without a cache
+        return PrefixPlan(prefix_cache, keys, lens)
+
     # -------------------------------------------------------------------------------- generate
     @torch.no_grad()
     def generate(self, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None, languages=None,
                  speakers=None, non_streaming_mode=False, max_new_tokens=4096, do_sample=True, top_k=50, top_p=1.0,
                  temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                  subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
-                 use_graph=True, max_batch=None, philox_ids=None, frame_caps=None, **kwargs):
+                 use_graph=True, max_batch=None, philox_ids=None, frame_caps=None, prefix_cache=None, **kwargs):
         """Same contract as Qwen3TTSForConditionalGeneration.generate (M:2022-2292):
         returns (list of [F_i,16] int64 codes, list of [F_i,H] last hidden states).
 
@@ -310,9 +341,15 @@ class TTSModel:
 
         Per-request sampling parameters (not in the reference): do_sample, top_k, top_p, temperature, the four
         subtalker_* values, repetition_penalty and seed each take a list with one entry per request (GenParams);
-        request i then gets the codes of the same call made with its values as scalars."""
+        request i then gets the codes of the same call made with its values as scalars.
+
+        prefix_cache (not in the reference): a qwen_tts.PrefixCache.  A request whose instruction is in
+        the cache adopts the instruction's talker K/V and prefills only the positions behind it; the first request
+        that misses stores it.  None (default): every prefill computes the whole prompt."""
+        lens = self._prefix_bind(prefix_cache)
         emb, mask, trail, pad = self.build_prompts(input_ids, languages, speakers, instruct_ids, non_streaming_mode,
-                                                   voice_clone_prompt, ref_ids)
+                                                   voice_clone_prompt, ref_ids, lens_out=lens)
+        plan = self._prefix_plan(prefix_cache, instruct_ids, voice_clone_prompt, lens)
         gp = GenParams(max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
                        subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
         B, P = emb.shape[0], emb.shape[1]
@@ -324,10 +361,11 @@ class TTSModel:
             max_batch = B if max_batch is None else max_batch
             codes, hid = [None] * B, [None] * B
             for i, c, h in self.engine.serve(reqs, pad, gp, slots=int(max_batch), use_graph=use_graph,
-                                             philox_ids=philox_ids):
+                                             philox_ids=philox_ids, prefix=plan):
                 codes[i], hid[i] = c, h
             return codes, hid
-        return self.engine.generate_from_embeds(emb, mask, trail, pad, gp, use_graph=use_graph, philox_ids=philox_ids)
+        return self.engine.generate_from_embeds(emb, mask, trail, pad, gp, use_graph=use_graph, philox_ids=philox_ids,
+                                                prefix=plan)
 
     @torch.no_grad()
     def teacher_forced(self, ref_codes, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None,
@@ -352,7 +390,7 @@ class TTSModel:
                temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
                first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None,
-               text_feed=None, sample_rate=None, pcm_format="f32", **kwargs):
+               text_feed=None, sample_rate=None, pcm_format="f32", prefix_cache=None, **kwargs):
         """Streaming generation (the reference has none): yields (row, pcm, last) as frames finish.
 
         Per row the chunks concatenate to the one-shot generate() + decode() PCM (Z:259-365): the reference
@@ -384,8 +422,11 @@ class TTSModel:
         rows, so the chunks concatenate to the resampled whole -- ceil(N * up / down) samples for the default's N --
         bit for bit whatever the chunking.  Outputs that need samples not generated yet (at most 10 * max(1, down / up)
         input samples' worth) follow with the next chunk; last=True flushes, so the last chunk may hold samples where
-        the default's is empty.  The stateless left_context form serves the default format only."""
+        the default's is empty.  The stateless left_context form serves the default format only.
+
+        prefix_cache: as in generate() -- with text_feed and with max_batch too."""
         fmt = self._output_format(sample_rate, pcm_format)
+        lens = self._prefix_bind(prefix_cache)
         if fmt is not None and left_context is not None:
             raise NotImplementedError("stream(left_context=...) with sample_rate / pcm_format: use the default "
                                       "stateful stream")
@@ -396,7 +437,7 @@ class TTSModel:
                                         GenParams(max_new_tokens, do_sample, top_k, top_p, temperature,
                                                   subtalker_dosample, subtalker_top_k, subtalker_top_p,
                                                   subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos,
-                                                  seed), fmt)
+                                                  seed), fmt, prefix_cache)
             return
         if max_batch is not None and input_ids is not None and len(input_ids) > int(max_batch):
             if left_context is not None:
@@ -407,7 +448,7 @@ class TTSModel:
                 subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed,
                 max_batch=max_batch, first_chunk_frames=first_chunk_frames,
                 chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, sample_rate=sample_rate,
-                pcm_format=pcm_format, **kwargs)
+                pcm_format=pcm_format, prefix_cache=prefix_cache, **kwargs)
             return
         dec = self.speech_tokenizer.model
         up = dec.total_upsample
@@ -420,7 +461,8 @@ class TTSModel:
             else None
         try:
             emb, mask, trail, pad = self.build_prompts(input_ids, languages, speakers, instruct_ids,
-                                                       non_streaming_mode, voice_clone_prompt, ref_ids)
+                                                       non_streaming_mode, voice_clone_prompt, ref_ids, lens_out=lens)
+            plan = self._prefix_plan(prefix_cache, instruct_ids, voice_clone_prompt, lens)
             gp = GenParams(max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
                            subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
             gp.check_rows(emb.shape[0])
@@ -441,13 +483,13 @@ class TTSModel:
         # the generation of the next one (~3 ms per frame), so playback started at the first packet never starves
         if left_context is None:
             yield from self._stream_stateful(dec, emb, mask, trail, pad, gp, B, eos, first_chunk_frames, chunk_frames,
-                                             use_graph, prefix, started, fmt=fmt)
+                                             use_graph, prefix, started, fmt=fmt, plan=plan)
             return
         if prefix is not None:
             raise NotImplementedError("stream(left_context=...) with voice-clone reference codes (ICL): use the "
                                       "default stateful stream")
         it = self.engine.decode_iter(emb, mask, trail, pad, gp, use_graph=use_graph, every=chunk_frames,
-                                     first=first_chunk_frames + 1, grow=True)
+                                     first=first_chunk_frames + 1, grow=True, prefix=plan)
         for sessions, frames, final in it:
             # codes of frames [0, frames) are final; column `frames` holds the next cb0 (EOS of finishing rows)
             codes = torch.cat([s.codes[:, :frames + 1] for s in sessions], 0)  # int32 [B, frames+1, 16], device
@@ -500,7 +542,8 @@ class TTSModel:
                 break
 
     def _stream_fed(self, feed, heads, instruct_ids, voice_clone_prompt, languages, speakers, non_streaming_mode,
-                    left_context, max_batch, first_chunk_frames, chunk_frames, use_graph, gp, fmt=None):
+                    left_context, max_batch, first_chunk_frames, chunk_frames, use_graph, gp, fmt=None,
+                    prefix_cache=None):
         """stream(text_feed=feed): the combinations it does not serve are refused before anything is allocated."""
         from .feed import TextFeed
         from .talker import TextGate
@@ -525,13 +568,15 @@ class TTSModel:
             if len(h) < 4:
                 raise ValueError(f"request {b}: a head is the three role ids plus at least one text id, got "
                                  f"{len(h)} ids")
+        lens = None if prefix_cache is None else []
         emb, mask, trail, pad = self.build_prompts(heads, languages, speakers, instruct_ids, False,
-                                                   voice_clone_prompt, None, open_text=True)
+                                                   voice_clone_prompt, None, open_text=True, lens_out=lens)
+        plan = self._prefix_plan(prefix_cache, instruct_ids, voice_clone_prompt, lens)
         gp.check_rows(B)
         gate = TextGate(feed, [len(h) - 4 for h in heads], self.config["tts_eos_token_id"])
         yield from self._stream_stateful(self.speech_tokenizer.model, emb, mask, trail, pad, gp, B,
                                          self.engine.tc["codec_eos_token_id"], first_chunk_frames, chunk_frames,
-                                         use_graph, gate=gate, fmt=fmt)
+                                         use_graph, gate=gate, fmt=fmt, plan=plan)
 
     @torch.no_grad()
     def serve_stream(self, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None, languages=None,
@@ -539,7 +584,7 @@ class TTSModel:
                      top_p=1.0, temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                      subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False,
                      seed=None, max_batch=8, first_chunk_frames=1, chunk_frames=8, use_graph=True, philox_ids=None,
-                     frame_caps=None, sample_rate=None, pcm_format="f32", **kwargs):
+                     frame_caps=None, sample_rate=None, pcm_format="f32", prefix_cache=None, **kwargs):
         """Streaming from the continuously batched route (the reference has neither): the requests are
         decoded through max_batch batch rows as generate(max_batch=...) decodes them, and each request's audio
         leaves as it is generated -- yields (request index, pcm, last).
@@ -554,16 +599,18 @@ class TTSModel:
         while the other rows carry on.  The sampling parameters take per-request lists as in generate().  Voice-clone
         prompts that carry reference codes (ICL) are not supported here; x-vector-only prompts are.
         sample_rate / pcm_format: as in stream() -- one resampler launch per codec feed for all slots, a slot's state
-        reset when its request changes."""
+        reset when its request changes.  prefix_cache: as in generate() -- the first prefill and every refill use it."""
         fmt = self._output_format(sample_rate, pcm_format)
         refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
         if refs is not None and any(r is not None for r in refs):
             raise NotImplementedError("serve_stream() / stream(max_batch=...) with voice-clone reference codes (ICL): "
                                       "use stream() without max_batch, or x-vector-only prompts")
+        lens = self._prefix_bind(prefix_cache)
         dec = self.speech_tokenizer.model
         up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
         emb, mask, trail, pad = self.build_prompts(input_ids, languages, speakers, instruct_ids, non_streaming_mode,
-                                                   voice_clone_prompt, ref_ids)
+                                                   voice_clone_prompt, ref_ids, lens_out=lens)
+        plan = self._prefix_plan(prefix_cache, instruct_ids, voice_clone_prompt, lens)
         gp = GenParams(max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
                        subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
         N, P = emb.shape[0], emb.shape[1]
@@ -584,7 +631,7 @@ class TTSModel:
         nz = [0] * B          # nonzero cb0 among the request's final frames
         try:
             for s, report in self.engine.serve_iter(reqs, pad, gp, slots=B, use_graph=use_graph, every=every,
-                                                    first=first, philox_ids=philox_ids):
+                                                    first=first, philox_ids=philox_ids, prefix=plan):
                 # per slot: the frames to feed, and the positions in that list at which the row (re)starts
                 todo, marks, ended = [[] for _ in range(B)], [{} for _ in range(B)], [False] * B
                 for b, r in enumerate(report):
@@ -704,7 +751,7 @@ class TTSModel:
         return pre, side, cs, fed
 
     def _stream_stateful(self, dec, emb, mask, trail, pad, gp, B, eos, first_chunk_frames, chunk_frames, use_graph,
-                         prefix=None, started=None, gate=None, fmt=None):
+                         prefix=None, started=None, gate=None, fmt=None, plan=None):
         """stream() on the incremental codec: every final frame is fed once to the decoder of its reference chunk
         and every sample computable from the frames fed so far is emitted -- 1920 n - 555 samples of a chunk after
         its n frames, i.e. no lookahead frame is waited for (the 555 samples that need it follow with the next
@@ -747,7 +794,7 @@ class TTSModel:
         # talker step that starts frame 1 (the first packet does not wait for it)
         it = self.engine.decode_iter(emb, mask, trail, pad, gp, use_graph=use_graph, every=chunk_frames,
                                      first=first_chunk_frames, grow=True, early_first=first_chunk_frames == 1,
-                                     gate=gate)
+                                     gate=gate, prefix=plan)
         try:
             for sessions, frames, final in it:
                 if side is not None:

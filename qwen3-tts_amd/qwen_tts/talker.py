@@ -16,11 +16,13 @@ from collections import OrderedDict, deque
 from dataclasses import dataclass
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 from . import _hip
 from . import kernels as K
 from .feed import TextFeedTimeout
+from .prefix import PrefixPlan, prefix_rows
 
 
 def _to_dev_i32(ids, dev) -> torch.Tensor:
@@ -488,6 +490,10 @@ class Session:
         # prompt length P -> static prefill buffers (+ captured graph once P repeats); LRU, PREFILL_CACHE lengths
         self.prefill = OrderedDict()
         self.slot_prefill = OrderedDict()  # P -> static single-request prefill buffers (serve() refills); LRU
+        # prefix-cache prefills (_prefill_cached): computed rows -> static buffers; LRU.  kv_layers: the K/V layer
+        # pointer table of qt_kv_prefix, built on first use
+        self.prefix_prefill = OrderedDict()
+        self.kv_layers = None
         self.busy = False  # held by a live decode_iter (a suspended stream() generator included)
         self.watch = None  # HandoffWatch armed at the last yield of decode_iter
         self.txt = None    # text-append buffers + captured append graph (TalkerEngine.append_text), built on first use
@@ -659,6 +665,11 @@ class TalkerEngine:
         self._sessions: Dict[tuple, List[Session]] = {}
         self._fence = None  # (event, stream) of the last frame issued (_fence_in / _fence_out)
         torch.cuda.synchronize()
+
+    def prefix_signature(self):
+        """What a PrefixCache binds to besides the engine itself: K/V dtype and talker layer geometry."""
+        t = self.talker
+        return (str(self.kv_dtype), t.n_layers, t.Hkv, t.D)
 
     def _proj_table(self, emb, Hc):
         """small_to_mtp(embedding table) (M:1299 applied row-wise) or the table itself, fp32 [V][Hc]."""
@@ -853,13 +864,14 @@ class TalkerEngine:
     # ---------------------------------------------------------------- G2/G3: prefill + decode loop
     def generate_from_embeds(self, embeds: torch.Tensor, mask: torch.Tensor, trailing: torch.Tensor,
                              tts_pad: torch.Tensor, gp: GenParams, use_graph: bool = True, on_frames=None,
-                             philox_ids=None):
+                             philox_ids=None, prefix: "Optional[PrefixPlan]" = None):
         """embeds fp32 [B,P,H] left-padded, mask [B,P] -> (codes list [F_i,16] int64 cpu, hidden list).
 
         philox_ids: optional per-row Philox stream ids (default the row index) -- a data-parallel shard passes its
-        requests' global indices, so every request draws the same stream whichever rank and row decode it."""
+        requests' global indices, so every request draws the same stream whichever rank and row decode it.
+        prefix: a PrefixPlan -- rows whose instruction is cached adopt its K/V and prefill the rest."""
         it = self.decode_iter(embeds, mask, trailing, tts_pad, gp, use_graph=use_graph, on_frames=on_frames,
-                              philox_ids=philox_ids)
+                              philox_ids=philox_ids, prefix=prefix)
         out = None
         for sessions, frames, final in it:
             if final:  # collected while the sessions are still held by this request
@@ -895,7 +907,7 @@ class TalkerEngine:
 
     def decode_iter(self, embeds, mask, trailing, tts_pad, gp: GenParams, use_graph: bool = True, on_frames=None,
                     every: int = 0, first: int = 0, grow: bool = False, philox_ids=None, early_first: bool = False,
-                    gate: "Optional[TextGate]" = None):
+                    gate: "Optional[TextGate]" = None, prefix: "Optional[PrefixPlan]" = None):
         """Prefill + frame loop as a generator: yields (sessions, frames_done, final) after `first` frames, then
         every `every` frames (0: only at the end; grow=True: intervals double from first - 1 up to `every`), and once
         at the end with final=True.  `sessions` is a one-element list (the batch's session); codes[:, :frames_done]
@@ -915,7 +927,7 @@ class TalkerEngine:
             s = self.session(B, P, max(max_frames, 1), gp)
             sessions.append(s)
             with K.use_workspace(s.ws):
-                self._prefill(s, embeds, mask, trailing, tts_pad, seed, philox_ids, gp=gp)
+                self._prefill(s, embeds, mask, trailing, tts_pad, seed, philox_ids, gp=gp, prefix=prefix)
             gate.bind(self, s, max_frames, use_graph)
             yield from self._frames(s, max_frames, use_graph, on_frames, every, first, grow, early_first, gate)
         finally:
@@ -1110,7 +1122,7 @@ class TalkerEngine:
 
     # ---------------------------------------------------------------- continuous batching
     def serve(self, requests, tts_pad, gp: GenParams, slots: int = 8, use_graph: bool = True, poll: int = 4,
-              philox_ids=None):
+              philox_ids=None, prefix: "Optional[PrefixPlan]" = None):
         """Continuous batching: decode `requests` through `slots` batch rows of one session, refilling a row with
         the next queued request as soon as its request ends (EOS, or max_new_tokens - 1 frames) instead of padding
         it with EOS until the whole batch ends as the reference's batched generate() does (M:2272-2292).
@@ -1128,8 +1140,9 @@ class TalkerEngine:
         The frame graph is the session's ordinary captured frame (per-row step / position counters); a refill is
         a single-request prefill into the slot's K/V rows between two graph replays.  The host learns which rows
         ended from pinned copies of the device flags every `poll` frames (no host sync on the decode stream).
-        philox_ids: optional Philox stream id per request (default its index i)."""
-        with self._serving(requests, tts_pad, gp, slots, philox_ids) as run:
+        philox_ids: optional Philox stream id per request (default its index i).  prefix: a PrefixPlan over the
+        requests: the first prefill and every refill adopt a cached instruction's K/V."""
+        with self._serving(requests, tts_pad, gp, slots, philox_ids, prefix) as run:
             if run is None:
                 return
             s, tab, refill = run
@@ -1194,7 +1207,7 @@ class TalkerEngine:
                     yield i, hc[:F].long(), hh[:F].clone()
 
     @contextlib.contextmanager
-    def _serving(self, requests, tts_pad, gp: GenParams, slots: int, philox_ids):
+    def _serving(self, requests, tts_pad, gp: GenParams, slots: int, philox_ids, prefix=None):
         """What a continuous-batching run is, however its progress is observed: the slot table, one session for
         min(slots, n) rows started by a batched prefill, the refill of a row, and at a normal end the hand-off check
         and `serve_stats`.  Yields (session, table, refill), or None for an empty request list (no session is taken);
@@ -1217,21 +1230,23 @@ class TalkerEngine:
             i = tab.retire(b)
             if i >= 0:
                 self.serve_queued[i] = time.perf_counter()
-                self._prefill_slot(s, b, requests[i], pids[i], gp.row_records(i, seed) if gp.per_row else None)
+                self._prefill_slot(s, b, requests[i], pids[i], gp.row_records(i, seed) if gp.per_row else None,
+                                   prefix=None if prefix is None else prefix.rows(i, i + 1))
             else:
                 s.finished[b:b + 1].fill_(1)  # idle slot: emits EOS until the session ends
 
         try:
             with K.use_workspace(s.ws):
                 self.serve_queued = dict.fromkeys(range(tab.B), time.perf_counter())
-                self._serve_start(s, requests, tab.B, tab.slot_p[0], tts_pad, seed, pids, gp)
+                self._serve_start(s, requests, tab.B, tab.slot_p[0], tts_pad, seed, pids, gp,
+                                  None if prefix is None else prefix.rows(0, tab.B))
                 yield s, tab, refill
                 check_handoffs([s])
                 self.serve_stats = {"frames": tab.frame, "slots": tab.B, "requests": n}
         finally:
             self.release([s])
 
-    def _serve_start(self, s: Session, requests, B, Pb, tts_pad, seed, pids, gp):
+    def _serve_start(self, s: Session, requests, B, Pb, tts_pad, seed, pids, gp, prefix=None):
         """The first B requests of a continuous-batching run start together: one batched prefill, left-padded to Pb
         tokens (as generate() does)."""
         H, dev = self.talker.H, self.dev
@@ -1244,11 +1259,11 @@ class TalkerEngine:
             emb[b, Pb - e.shape[0]:] = e
             mask[b, Pb - e.shape[0]:] = 1
             trail[b, :tr.shape[0]] = tr
-        self._prefill(s, emb, mask, trail, tts_pad, seed, pids[:B], gp=gp)
+        self._prefill(s, emb, mask, trail, tts_pad, seed, pids[:B], gp=gp, prefix=prefix)
         s.hiddens[:, 0].copy_(s.past_hidden)
 
     def serve_iter(self, requests, tts_pad, gp: GenParams, slots: int = 8, use_graph: bool = True, every: int = 8,
-                   first: int = 1, philox_ids=None):
+                   first: int = 1, philox_ids=None, prefix: "Optional[PrefixPlan]" = None):
         """serve() observed as it runs (TTSModel.serve_stream): the same session, prefills, frame graph, refills and
         Philox streams, so request i gets the codes serve() gives it, but progress is reported every `every` frame
         replays, and `first` replays after a slot's refill, instead of whole requests at their end.
@@ -1260,7 +1275,7 @@ class TalkerEngine:
         order before it resumes the generator, which then refills the ended slots.  One host sync per report (the
         cb0 columns of the new frames and the hand-off flag word, copied together): a hand-off give-up raises
         HandoffError before the frames it covers are reported."""
-        with self._serving(requests, tts_pad, gp, slots, philox_ids) as run:
+        with self._serving(requests, tts_pad, gp, slots, philox_ids, prefix) as run:
             if run is None:
                 return
             s, tab, refill = run
@@ -1301,11 +1316,12 @@ class TalkerEngine:
                         seen[b], fresh[b] = 0, True
                         refill(b)
 
-    def _prefill_slot(self, s: Session, b: int, req, i: int, records=None):
+    def _prefill_slot(self, s: Session, b: int, req, i: int, records=None, prefix=None):
         """Start a request in batch row b (Philox stream id i): per-row state reset, single-request talker prefill into
         row b's K/V (positions 0..P-1, no left padding), first token (M:1746-1800, 2044).  records: the request's
         (talker, sub-talker) sampler records of a per-row session, written to row b of its tables in stream order --
-        behind the frames already queued for the slot's previous request, before this one's first sample."""
+        behind the frames already queued for the slot's previous request, before this one's first sample.
+        prefix: a one-request PrefixPlan -- the prefill then runs through _prefill_cached."""
         emb, trail = req[0], req[1]
         P, H = int(emb.shape[0]), self.talker.H
         t, dev = self.talker, self.dev
@@ -1327,6 +1343,10 @@ class TalkerEngine:
         tr.copy_(s.pad_embed.view(1, H).expand_as(tr))
         nt = min(int(trail.shape[0]), tr.shape[0])
         tr[:nt] = trail[:nt].to(dev).float()
+        if prefix is not None:
+            self._prefill_cached(s, prefix, emb.reshape(1, P, H), b)
+            s.hiddens[b, 0].copy_(s.past_hidden[b])
+            return
         pre = _lru_get(s.slot_prefill, P)
         if pre is None:
             i32 = lambda *z: torch.zeros(*z, dtype=torch.int32, device=dev)  # noqa: E731
@@ -1344,10 +1364,11 @@ class TalkerEngine:
         K.gemm(s.past_hidden[b:b + 1], self.codec_head, s.logits[b:b + 1], 1, H, self.V)
         self._sample_talker(s, s.logits, 0, 99, b, b + 1)
 
-    def _prefill(self, s: Session, embeds, mask, trailing, tts_pad, seed: int, philox_ids=None, gp=None):
+    def _prefill(self, s: Session, embeds, mask, trailing, tts_pad, seed: int, philox_ids=None, gp=None, prefix=None):
         """Talker prefill of one row group (M:1746-1800 positions, M:2044 first token) into session s.
         philox_ids: per-row Philox stream ids (default the row index).  gp: the call's parameters -- a per-row
-        session's tables get the records of requests 0 .. B-1 before the first sample."""
+        session's tables get the records of requests 0 .. B-1 before the first sample.  prefix: a PrefixPlan over the
+        B rows -- the forward pass then runs through _prefill_cached (the decode counters are set as without)."""
         B, P, H = embeds.shape
         dev = self.dev
         s.P = P  # padded prompt length: every row's decode keys are <= P + frames + 1
@@ -1377,6 +1398,21 @@ class TalkerEngine:
         n_real = mask.sum(-1)
         n_pads = P - n_real
         rope_delta = (max_pos + 1 - n_real).long() - n_pads
+        if prefix is not None:
+            self._prefill_cached(s, prefix, embeds, 0)
+        else:
+            self._prefill_full(s, embeds, mask, pos, n_pads)
+        # decode counters: step 0, one token generated, pos = P + delta, kv_pos = P, len = P + 1
+        s.n_gen.fill_(1)  # a device fill: item assignment uploads a host scalar and waits for the prefill
+        s.meta["rope_pos"].copy_((P + rope_delta).to(torch.int32))
+        s.meta["kv_pos"].fill_(P)
+        s.meta["row_len"].fill_(P + 1)
+        s.meta["row_start"].copy_(n_pads.to(torch.int32))
+
+    def _prefill_full(self, s: Session, embeds, mask, pos, n_pads):
+        """The talker prefill over every position of the left-padded batch (static buffers per prompt length)."""
+        B, P, H = embeds.shape
+        dev = self.dev
         R = B * P
         pre = _lru_get(s.prefill, P)
         if pre is None:  # static buffers of this prompt length (a captured graph binds their addresses)
@@ -1400,12 +1436,82 @@ class TalkerEngine:
             # prefill: ~170 launches replayed instead of issued from Python (host-bound, ~4.6 ms at B=8)
             if PREFILL_GRAPH and pre["uses"] >= 2:
                 pre["graph"] = self._capture(s, lambda: self._prefill_compute(s, pre, B, P))
-        # decode counters: step 0, one token generated, pos = P + delta, kv_pos = P, len = P + 1
-        s.n_gen.fill_(1)  # a device fill: item assignment uploads a host scalar and waits for the prefill
-        s.meta["rope_pos"].copy_((P + rope_delta).to(torch.int32))
-        s.meta["kv_pos"].fill_(P)
-        s.meta["row_len"].fill_(P + 1)
-        s.meta["row_start"].copy_(n_pads.to(torch.int32))
+
+    def _prefill_cached(self, s: Session, plan: PrefixPlan, embeds, b0: int):
+        """Talker prefill with a prefix cache, for the batched prefill (b0 = 0, embeds [B, P, H]
+        left-padded) and the slot refill (embeds [1, P, H], P its length, batch row b0) alike.  Row r of `embeds` is
+        batch row b0 + r, with plan.lens[r] real positions.  A row whose instruction (plan.keys[r]) is cached adopts the
+        entry into its K/V at [n_pads, n_pads + N) and computes only the positions behind it; the rows of all batch
+        rows are packed (prefix_rows) and go through the stack's generic branch -- qt_qkv_post + qt_attention over
+        per-row (batch, start, length), keys partly adopted.  Afterwards the first missing row of each new key exports
+        its instruction's K/V into a new entry (two rows missing one key both compute in full).
+
+        Issued eagerly, not captured: the set of computed rows changes with the hits.  The host builds one row table
+        (numpy) and uploads it in one pinned copy; adopt and export are one qt_kv_prefix launch each.  Entry blocks are
+        allocated, filled, read and freed in stream order on this stream; an entry made on another stream is waited
+        for (its event) and guarded by record_stream, so an evicted block is not reused under a queued adopt."""
+        t, dev, H = self.talker, self.dev, self.talker.H
+        nb, P = int(embeds.shape[0]), int(embeds.shape[1])
+        embeds = embeds.to(dev, torch.float32)
+        cache, n_real = plan.cache, plan.lens
+        if len(n_real) != nb:
+            raise ValueError(f"prefix plan of {len(n_real)} requests for {nb} batch rows")
+        cur = torch.cuda.current_stream(dev)
+        C, hits, first_miss = [0] * nb, [], {}
+        for r, key in enumerate(plan.keys):
+            if key is None or not 0 < len(key) < n_real[r]:
+                continue
+            e = cache.lookup(key)
+            if e is not None:
+                C[r] = e.n
+                hits.append((r, e))
+            elif key not in first_miss:
+                first_miss[key] = r
+        tab = prefix_rows(P, n_real, C)
+        R = int(tab["rope_pos"].shape[0])
+        # one upload: the five row arrays, each computed position's index in the flattened batch, the last-row indices
+        names = ("rope_pos", "kv_pos", "row_len", "row_start", "row_batch", "src")
+        tab["row_batch"] = tab["row_batch"] + b0
+        host = np.concatenate([tab[k] for k in names] + [tab["last"].astype(np.int32)])
+        blk = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+        meta = {k: blk[i * R:(i + 1) * R] for i, k in enumerate(names)}
+        src, last = meta.pop("src"), blk[6 * R:]
+        pre = _lru_get(s.prefix_prefill, R)
+        if pre is None:
+            pre = self._prefill_buffers(R, None)
+            _lru_put(s.prefix_prefill, R, pre)
+        torch.index_select(embeds.reshape(nb * P, H), 0, src, out=pre["x"])
+        if pre["x16"] is not None:
+            pre["x16"].copy_(pre["x"])
+        if s.kv_layers is None:
+            s.kv_layers = K.kv_layer_table(s.kv)
+        pads = [P - n for n in n_real]
+        jobs = []
+        for r, e in hits:
+            if e.stream is not None and e.stream != cur:
+                cur.wait_event(e.event)
+                e.block.record_stream(cur)
+            jobs.append((e.block, b0 + r, pads[r], e.n, _hip.KV_ADOPT))
+        K.kv_prefix(jobs, s.kv_layers, s.kv)
+        t.forward(pre["x"], R, meta, s.kv, pre["sc"], s.Lmax, P, x16=pre["x16"])
+        ph, lg = s.past_hidden[b0:b0 + nb], s.logits[b0:b0 + nb]
+        K.rmsnorm(pre["x"].index_select(0, last), t.norm, t.eps, ph, nb, H)
+        K.gemm(ph, self.codec_head, lg, nb, H, self.V)
+        self._sample_talker(s, s.logits, 0, 99, b0, b0 + nb)
+        jobs, made = [], []
+        for key, r in first_miss.items():
+            N = len(key)
+            if not cache.fits(2 * t.n_layers * t.Hkv * N * t.D * s.kv[0][0].element_size()):
+                continue  # larger than the whole cache: not stored
+            block = torch.empty(2, t.n_layers, t.Hkv, N, t.D, dtype=self.kv_dtype, device=dev)
+            jobs.append((block, b0 + r, pads[r], N, _hip.KV_EXPORT))
+            made.append((key, N, block))
+        if jobs:
+            K.kv_prefix(jobs, s.kv_layers, s.kv)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            for key, N, block in made:
+                cache.store(key, N, block, event=ev, stream=cur)
 
     def _prefill_buffers(self, R: int, meta: dict) -> dict:
         """Static buffers of a talker prefill over R rows: the fp32 residual stream, the scratch, the row arrays the

@@ -19,8 +19,15 @@ from the moment its prefill was queued to its first chunk being complete on the 
 defaults are the codec's own 24 kHz fp32.  --ab 16000:s16,48000:f32 runs those formats beside the selected one in the
 same process, alternating within every repetition, one line each; --only-stream skips the first two schedules.
 
+--voices K draws every request's instruction from K distinct ones (a voice product's traffic; 0, the default, gives
+every request its own).  --prefix-cache runs the stream schedule with and without a qwen_tts.PrefixCache in
+the same process, alternating within every repetition, one line each; the cache lives for the whole process, so the
+measured runs are warm (their hits and misses are in the line).  --streaming-text puts only the first text token into
+the prefill (non_streaming_mode=False) instead of the wrapper's default.
+
     python tools/serve_bench.py [--requests 8] [--slots 8] [--extra-slots 16,32] [--stream]
         [--sample-rate 16000 --pcm s16] [--ab 16000:s16,48000:f32] [--only-stream]
+        [--voices 8] [--prefix-cache] [--streaming-text]
 """
 from __future__ import annotations
 
@@ -40,16 +47,21 @@ sys.path.insert(0, REPO)
 from bench import make_weights  # noqa: E402
 
 
-def workload(n, seed=4):
+def workload(n, seed=4, voices=0):
+    """n requests (text ids, instruct ids, frames).  voices = K > 0: K instructions ~ U[10, 60] tokens are drawn first
+    (a generator of their own, so texts and frame counts are those of the default workload) and every request picks
+    one of them at random."""
     g = np.random.default_rng([seed, 99])
+    gv = np.random.default_rng([seed, 98])
+    wrap = lambda body: torch.tensor([[151644, 872, 198] + body + [151645, 198]], dtype=torch.long)  # noqa: E731
+    vs = [wrap(gv.integers(1000, 150000, int(gv.integers(10, 61))).tolist()) for _ in range(voices)]
     reqs = []
     for i in range(n):
         t, k, f = int(g.integers(40, 301)), int(g.integers(10, 61)), int(g.integers(64, 321))
         body = g.integers(1000, 150000, t).tolist()
         ids = torch.tensor([[151644, 77091, 198] + body + [151645, 198, 151644, 77091, 198]], dtype=torch.long)
-        ins = torch.tensor([[151644, 872, 198] + g.integers(1000, 150000, k).tolist() + [151645, 198]],
-                           dtype=torch.long)
-        reqs.append((ids, ins, f))
+        ins = wrap(g.integers(1000, 150000, k).tolist())
+        reqs.append((ids, vs[int(gv.integers(0, voices))] if voices else ins, f))
     return reqs
 
 
@@ -66,16 +78,21 @@ def main():
     ap.add_argument("--pcm", default="f32", choices=["f32", "s16"], help="sample format of the stream schedule")
     ap.add_argument("--ab", default="", help="more rate:format pairs for the stream schedule, run alternately")
     ap.add_argument("--only-stream", action="store_true", help="skip the padded and serve schedules")
+    ap.add_argument("--voices", type=int, default=0, help="draw the instructions from this many distinct ones")
+    ap.add_argument("--prefix-cache", action="store_true", help="stream schedule with and without a PrefixCache")
+    ap.add_argument("--streaming-text", action="store_true", help="non_streaming_mode=False (default True)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    from qwen_tts import Qwen3TTSModel
+    from qwen_tts import PrefixCache, Qwen3TTSModel
     from qwen_tts.talker import GenParams
     _, W, CW = make_weights(a.preset, dev, 1, 0)
     tts = Qwen3TTSModel.from_pretrained(f"synthetic:{a.preset}", device_map=str(dev), dtype=torch.bfloat16,
                                         weights=W, codec_weights=CW)
     del W, CW
     m, eng = tts.model, tts.model.engine
-    reqs = workload(a.requests)
+    reqs = workload(a.requests, voices=a.voices)
+    nsm = not a.streaming_text
+    cache = PrefixCache() if a.prefix_cache else None
     F = [f for _, _, f in reqs]
     audio_s = 0.08 * sum(F)
     # F = max_new_tokens - 1 frames, as in bench.py; every row runs with ignore_eos so its length is exact
@@ -84,7 +101,7 @@ def main():
 
     def prompts(sel):
         return m.build_prompts([reqs[i][0] for i in sel], ["english"] * len(sel), None, [reqs[i][1] for i in sel],
-                               True)
+                               nsm)
 
     def padded(slots, seed):
         codes = [None] * len(reqs)
@@ -112,12 +129,18 @@ def main():
 
     formats = [(a.sample_rate, a.pcm)] + [(int(x.split(":")[0]), x.split(":")[1]) for x in a.ab.split(",") if x]
 
-    def stream(slots, seed, fmt=formats[0]):
+    # (format, with the prefix cache) of every stream run
+    variants = [(fmt, c) for fmt in formats for c in ((False, True) if a.prefix_cache else (False,))]
+
+    def stream(slots, seed, var=variants[0]):
         """serve_stream: returns the samples received per request; first-chunk latencies go to first_ms"""
+        fmt, cached = var
         got, lat = [0] * len(reqs), {}
         out = {} if fmt == (None, "f32") else dict(sample_rate=fmt[0], pcm_format=fmt[1])
+        if cached:
+            out["prefix_cache"] = cache
         it = m.serve_stream(input_ids=[r[0] for r in reqs], instruct_ids=[r[1] for r in reqs],
-                            languages=["english"] * len(reqs), non_streaming_mode=True, max_new_tokens=max(F) + 1,
+                            languages=["english"] * len(reqs), non_streaming_mode=nsm, max_new_tokens=max(F) + 1,
                             seed=seed, frame_caps=F, max_batch=slots, first_chunk_frames=1,
                             chunk_frames=a.chunk_frames, **gen, **out)
         for i, pcm, last in it:
@@ -129,18 +152,24 @@ def main():
         return got
 
     def run_stream(slots):
-        """{format: (wall times, first-chunk latencies)}; the formats alternate within every repetition"""
-        res = {fmt: ([], []) for fmt in formats}
-        for fmt in formats:
-            stream(slots, 1, fmt)  # warmup (graph captures, sessions, codec slot)
+        """{(format, cached): (wall times, first-chunk latencies, [hits, misses] of the measured runs)}; the variants
+        alternate within every repetition"""
+        res = {var: ([], [], [0, 0]) for var in variants}
+        for var in variants:
+            stream(slots, 1, var)  # warmup (graph captures, sessions, codec slot; fills the prefix cache)
         for r in range(a.reps):
-            for fmt in formats:
+            for var in variants:
+                fmt = var[0]
+                before = cache.stats if var[1] else None
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                got = stream(slots, 10 + r, fmt)
+                got = stream(slots, 10 + r, var)
                 torch.cuda.synchronize()
-                res[fmt][0].append(time.perf_counter() - t0)
-                res[fmt][1].extend(first_ms)
+                res[var][0].append(time.perf_counter() - t0)
+                res[var][1].extend(first_ms)
+                if var[1]:
+                    res[var][2][0] += cache.stats["hits"] - before["hits"]
+                    res[var][2][1] += cache.stats["misses"] - before["misses"]
                 # every frame's 1920 samples but each reference chunk's last 555 (fewer only where a cb0 is 0), at
                 # the output rate
                 rate = 24000 if fmt[0] is None else fmt[0]
@@ -177,11 +206,15 @@ def main():
                                           "F U[64,320], sampling, ignore_eos + per-request cap, + codec decode"}),
                   flush=True)
     if a.stream:
-        for slots, (fmt, (ts, lats)) in ((s, kv) for s in slot_list for kv in run_stream(s).items()):
+        for slots, ((fmt, cached), (ts, lats, hm)) in ((s, kv) for s in slot_list for kv in run_stream(s).items()):
             dt = float(np.median(ts))
+            pc = {} if not a.prefix_cache else {"prefix_cache": cached}
+            if cached:
+                pc.update(hits=hm[0], misses=hm[1], cache=cache.stats)
             st = getattr(eng, "serve_stats", {})
             print(json.dumps({"schedule": "serve_stream", "slots": slots, "requests": a.requests,
-                              "sample_rate": 24000 if fmt[0] is None else fmt[0], "pcm": fmt[1],
+                              "sample_rate": 24000 if fmt[0] is None else fmt[0], "pcm": fmt[1], **pc,
+                              "voices": a.voices, "non_streaming_mode": nsm,
                               "chunk_frames": a.chunk_frames, "frames_replayed": st.get("frames"),
                               "frames_min": -(-sum(F) // slots), "audio_s": round(audio_s, 2),
                               "wall_s": round(dt, 4), "audio_s_per_s": round(audio_s / dt, 2),
