@@ -10,8 +10,10 @@ from .inference.qwen3_tts_model import (Qwen3TTSModel, VoiceClonePromptItem, loa
                                        save_voice_clone_prompt)
 from .inference.qwen3_tts_tokenizer import Qwen3TTSTokenizer  # noqa: E402,F401
 from .feed import TextFeed, TextFeedTimeout  # noqa: E402,F401
+from .live import RequestQueue  # noqa: E402,F401
 from .resample import PcmResampler  # noqa: E402,F401
 from .prefix import PrefixCache  # noqa: E402,F401
 
 __all__ = ["__version__", "Qwen3TTSModel", "Qwen3TTSTokenizer", "VoiceClonePromptItem", "load_voice_clone_prompt",
-           "save_voice_clone_prompt", "TextFeed", "TextFeedTimeout", "PcmResampler", "PrefixCache"]
+           "save_voice_clone_prompt", "TextFeed", "TextFeedTimeout", "RequestQueue", "PcmResampler",
+           "PrefixCache"]

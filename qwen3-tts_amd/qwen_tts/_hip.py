@@ -149,6 +149,20 @@ class KvPrefixJob(ctypes.Structure):
     _fields_ = [("block", c_void_p), ("row", c_int), ("pos", c_int), ("n", c_int), ("dir", c_int)]
 
 
+ROW_SAVE, ROW_RESTORE = 0, 1  # QT_ROW_*
+ROW_STATE_MAX_REGIONS = 16
+
+
+class RowRegion(ctypes.Structure):
+    """qt_row_region: one piece of per-row state of a qt_row_state call"""
+    _fields_ = [("base", c_void_p), ("stride", c_ll), ("bytes", c_ll)]
+
+
+class RowStateArgs(ctypes.Structure):
+    _fields_ = [("n_regions", c_int), ("B", c_int), ("dir", c_int), ("reserved", c_int), ("mask", c_ull),
+                ("stash", c_void_p), ("stash_row_bytes", c_ll), ("regions", RowRegion * ROW_STATE_MAX_REGIONS)]
+
+
 EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decode_attention", "qt_decode_attn_ws_bytes",
            "qt_rmsnorm_rec", "qt_small_prefill_attention",
            "qt_decode_attn_oproj", "qt_attn_oproj_ws_bytes", "qt_attn_oproj_resident_blocks",
@@ -157,6 +171,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_talker_tail_supported", "qt_codec_resunit", "qt_codec_resunit_supported",
            "qt_sample", "qt_sample_row_bytes", "qt_sample_args_bytes", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
            "qt_stream_window", "qt_stream_rows", "qt_trail_append", "qt_kv_prefix",
+           "qt_row_state", "qt_row_state_row_bytes",
            "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
@@ -209,6 +224,7 @@ def load_library(path: str = LIB_PATH):
         "qt_advance_rows": [P, c_int, c_int, c_int, P],
         "qt_trail_append": [P, P, P, c_int, c_int, c_int, c_int, P],
         "qt_kv_prefix": [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
+        "qt_row_state": [P, P], "qt_row_state_row_bytes": [P],
         "qt_stream_window": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
         "qt_stream_rows": [P, P, c_int, c_int, P, P, P],
         "qt_rvq_gather": [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P],

@@ -20,6 +20,7 @@ import torch
 from .. import audio as _audio
 from .. import kernels as _kernels
 from .. import resample as _resample
+from ..live import SAMPLING_DEFAULTS, RequestQueue
 from ..model import TTSModel
 from ..text import load_processor
 from ..speaker import speaker_specs
@@ -79,6 +80,36 @@ def load_voice_clone_prompt(path: str) -> List[VoiceClonePromptItem]:
         items.append(VoiceClonePromptItem(ref_code=ref_code, ref_spk_embedding=spk, x_vector_only_mode=xv,
                                           icl_mode=bool(d.get("icl_mode", not xv)), ref_text=d.get("ref_text", None)))
     return items
+
+
+class _TextRequestQueue(RequestQueue):
+    """Qwen3TTSModel.request_queue(): a RequestQueue whose submit() also takes strings."""
+
+    def __init__(self, wrapper: "Qwen3TTSModel", timeout: float):
+        super().__init__(timeout)
+        self._wrapper, self.processor = wrapper, wrapper.processor
+
+    def submit(self, input_ids=None, *, text=None, instruct=None, language=None, speaker=None, open_text=False,
+               non_streaming_mode=None, **kwargs) -> int:
+        w = self._wrapper
+        if (text is None) == (input_ids is None):
+            raise ValueError("submit() takes either text=... or input_ids")
+        if text is not None:
+            ids, ins, langs, spks = w._custom_voice_inputs(text, speaker, language, instruct)
+            if len(ids) != 1:
+                raise ValueError("submit() takes one utterance per request")
+            input_ids, language, speaker = ids[0], langs[0], spks[0]
+            if ins[0] is not None:
+                kwargs["instruct_ids"] = ins[0]
+            if open_text:  # the head: role ids + the first piece, no template suffix
+                input_ids = w._tokenize_texts([f"<|im_start|>assistant\n{text}"])[0]
+        if non_streaming_mode is None:
+            non_streaming_mode = not open_text
+        sampling = {k: kwargs.pop(k, None) for k in SAMPLING_DEFAULTS if k != "seed"}
+        merged = w._merge_generate_kwargs(**sampling)
+        merged.pop("max_new_tokens")
+        return super().submit(input_ids, language=language, speaker=speaker, open_text=open_text,
+                              non_streaming_mode=non_streaming_mode, **merged, **kwargs)
 
 
 class Qwen3TTSModel:
@@ -471,6 +502,31 @@ class Qwen3TTSModel:
         feed = TextFeed(rows=rows, timeout=timeout)
         feed.processor = self.processor
         return feed
+
+    def request_queue(self, timeout: float = 30.0):
+        """A qwen_tts.RequestQueue for serve_live() that also takes strings:
+        submit(text=..., instruct=..., language=..., speaker=..., open_text=False, **sampling) tokenizes as stream()
+        does (with open_text, `text` is the first piece and the rest follows through push_text / close_text), and
+        fills the sampling parameters a request leaves out from generation_config.json.  non_streaming_mode defaults
+        to True as in generate_custom_voice(), and to False with open_text."""
+        return _TextRequestQueue(self, timeout)
+
+    @torch.no_grad()
+    def serve_live(self, queue, max_batch=8, max_prompt=512, first_chunk_frames=1, chunk_frames=8, sample_rate=None,
+                   pcm_format="f32", prefix_cache=None, max_new_tokens=None, **kwargs):
+        """New surface (no reference counterpart): serve the requests of `queue` (self.request_queue()) as they
+        arrive, through max_batch continuously batched rows (TTSModel.serve_live).  Yields (request id, pcm chunk
+        np.float32 -- np.int16 with pcm_format="s16" --, sample rate, is_last) until the queue is closed and every
+        request is over.  kwargs: eos_token_id, ignore_eos, seed, use_graph."""
+        sr = self._output_format(sample_rate, pcm_format)
+        if self.model.tts_model_type != "custom_voice":
+            raise ValueError(f"model with tts_model_type: {self.model.tts_model_type} does not support serve_live")
+        mnt = self._merge_generate_kwargs(max_new_tokens=max_new_tokens)["max_new_tokens"]
+        for i, pcm, last in self.model.serve_live(queue, max_batch=max_batch, max_prompt=max_prompt,
+                                                  max_new_tokens=mnt, first_chunk_frames=first_chunk_frames,
+                                                  chunk_frames=chunk_frames, sample_rate=sample_rate,
+                                                  pcm_format=pcm_format, prefix_cache=prefix_cache, **kwargs):
+            yield i, (pcm if pcm.dtype == torch.int16 else pcm.to(torch.float32)).cpu().numpy(), sr, last
 
     def get_supported_speakers(self) -> Optional[List[str]]:
         s = self._supported_speakers_set()

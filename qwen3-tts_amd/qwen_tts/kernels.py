@@ -559,6 +559,30 @@ def kv_prefix(jobs, layers, kv):
                                   _hip.dtype_code(kv[0][0].dtype), stream()), "qt_kv_prefix")
 
 
+class RowState:
+    """The region table of qt_row_state and its stash: regions = [(tensor, row stride in bytes, bytes per row)], row 0
+    of a region at the tensor's data pointer; B batch rows.  The tensors are kept alive with the table.  `stash` is a
+    zeroed uint8 [B][row_bytes] device buffer unless the caller brings one (tests put guard bytes around it)."""
+
+    def __init__(self, regions, B: int, device, stash=None):
+        self.regions, self.B = list(regions), int(B)
+        a = self.args = _hip.RowStateArgs()
+        a.n_regions, a.B = len(self.regions), self.B
+        for r, (t, stride, nbytes) in enumerate(self.regions[:_hip.ROW_STATE_MAX_REGIONS]):
+            a.regions[r] = _hip.RowRegion(ptr(t), int(stride), int(nbytes))
+        self.row_bytes = int(_hip.lib().qt_row_state_row_bytes(ctypes.byref(a)))
+        check(min(self.row_bytes, 0), "qt_row_state_row_bytes")
+        self.stash = torch.zeros(self.B, self.row_bytes, dtype=torch.uint8, device=device) if stash is None else stash
+        a.stash, a.stash_row_bytes = ptr(self.stash), self.row_bytes
+
+
+def row_state(rs: RowState, mask: int, direction: int):
+    """One qt_row_state launch on the current stream: the rows whose bit is set in `mask` are saved to rs.stash
+    (_hip.ROW_SAVE) or put back from it (_hip.ROW_RESTORE).  An empty mask launches nothing."""
+    rs.args.mask, rs.args.dir = int(mask), int(direction)
+    check(_hip.lib().qt_row_state(ctypes.byref(rs.args), stream()), "qt_row_state")
+
+
 def stream_window(hist, x, xin, B, H, n, C, rows_per_frame, head, rows):
     """xin [B][H+n][C] = [hist | x] per the row table rows [2][B] (nrow, begin), then hist = xin[:, m_b:m_b + H]
     (m_b = nrow[b] * rows_per_frame); a beginning row reads zero history and zeros for its first `head` rows."""

@@ -606,8 +606,6 @@ class TTSModel:
             raise NotImplementedError("serve_stream() / stream(max_batch=...) with voice-clone reference codes (ICL): "
                                       "use stream() without max_batch, or x-vector-only prompts")
         lens = self._prefix_bind(prefix_cache)
-        dec = self.speech_tokenizer.model
-        up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
         emb, mask, trail, pad = self.build_prompts(input_ids, languages, speakers, instruct_ids, non_streaming_mode,
                                                    voice_clone_prompt, ref_ids, lens_out=lens)
         plan = self._prefix_plan(prefix_cache, instruct_ids, voice_clone_prompt, lens)
@@ -620,6 +618,16 @@ class TTSModel:
                 for i in range(N)]
         B = max(1, min(int(max_batch), N))
         first, every = max(1, int(first_chunk_frames)), max(1, int(chunk_frames))
+        yield from self._serve_codec(
+            self.engine.serve_iter(reqs, pad, gp, slots=B, use_graph=use_graph, every=every, first=first,
+                                   philox_ids=philox_ids, prefix=plan), B, first, every, fmt)
+
+    def _serve_codec(self, reports, B, first, every, fmt):
+        """The codec half of serve_stream() and serve_live(): consumes the talker's (session, report) items
+        (TalkerEngine.serve_iter / serve_live_iter) and yields (request, pcm, last).  A row without new frames in a
+        report -- idle, or held -- rides along.  An item (None, [requests]) names requests that end without audio."""
+        dec = self.speech_tokenizer.model
+        up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
         caps = sorted({first, every})  # feed capacities (one captured codec graph each)
         dev = self.device
         rs = dec.row_stream(B, RX + RC, caps[-1])
@@ -630,8 +638,12 @@ class TTSModel:
         cum = [0] * B         # samples handed out for the slot's request
         nz = [0] * B          # nonzero cb0 among the request's final frames
         try:
-            for s, report in self.engine.serve_iter(reqs, pad, gp, slots=B, use_graph=use_graph, every=every,
-                                                    first=first, philox_ids=philox_ids, prefix=plan):
+            for s, report in reports:
+                if s is None:
+                    for i in report:
+                        yield i, torch.zeros(0, dtype=torch.int16 if fmt is not None and fmt[1] == "s16"
+                                             else torch.float32, device=dev), True
+                    continue
                 # per slot: the frames to feed, and the positions in that list at which the row (re)starts
                 todo, marks, ended = [[] for _ in range(B)], [{} for _ in range(B)], [False] * B
                 for b, r in enumerate(report):
@@ -690,6 +702,74 @@ class TTSModel:
                         yield from self._resampled(out, pcm, pend, req)
         finally:
             rs.close()
+            reports.close()
+
+    @torch.no_grad()
+    def serve_live(self, queue, max_batch=8, max_prompt=512, max_new_tokens=4096, eos_token_id=None, ignore_eos=False,
+                   seed=None, first_chunk_frames=1, chunk_frames=8, use_graph=True, sample_rate=None, pcm_format="f32",
+                   prefix_cache=None):
+        """Live serving (the reference has none): serve_stream() over an open request stream.  `queue` is
+        a qwen_tts.RequestQueue; requests are submitted to it while this generator runs, each with its own sampling
+        parameters, and decoded through max_batch batch rows as they arrive -- yields (request id, pcm, last).
+
+        A whole-text request gets the codes generate(max_batch=...) gives the request of that index and seed, and the
+        audio serve_stream() gives it.  An open-text request (submit(head, open_text=True): the three role ids and at
+        least one text id) receives its text through queue.push / close_text while it decodes, as
+        stream(text_feed=...) does, and decodes what the whole-text request decodes in streaming-text mode; while its
+        next token is missing its row is held and the other rows go on (TalkerEngine._run_frame_held).  It still gets
+        a one-frame first packet from its first text id alone.  A request starved for queue.timeout seconds is
+        retired with the audio it has (queue.timed_out), as is a cancelled one; one that cannot be served -- a prompt
+        longer than max_prompt, voice-clone reference codes (ICL), open_text with non_streaming_mode, an unknown
+        speaker or language -- is yielded once as (id, empty, True) with the reason in queue.rejected[id].  None of
+        them ends the loop: it ends when the queue is closed and every request is over.
+
+        Only the thread running this generator issues GPU work, prompt assembly included (at admission).  max_prompt:
+        the K/V capacity per row in prompt positions.  seed: the call's seed, for requests that name none; request i
+        draws Philox stream i.  sample_rate / pcm_format / prefix_cache: as in serve_stream()."""
+        from .live import RequestQueue
+        if not isinstance(queue, RequestQueue):
+            raise ValueError(f"queue must be a qwen_tts.RequestQueue, got {type(queue).__name__}")
+        fmt = self._output_format(sample_rate, pcm_format)
+        self._prefix_bind(prefix_cache)
+        B = int(max_batch)
+        if not 1 <= B <= 64:
+            raise ValueError(f"serve_live takes 1..64 batch rows, got {max_batch}")
+        first, every = max(1, int(first_chunk_frames)), max(1, int(chunk_frames))
+        cfg = self.config
+        one = lambda v: (v,)  # noqa: E731 -- every ROW_FIELD as a list: the session reads per-row tables
+        gp = GenParams(max_new_tokens, one(True), one(50), one(1.0), one(0.9), one(True), one(50), one(1.0), one(0.9),
+                       eos_token_id, one(1.05), ignore_eos, seed)
+        pad = self.engine.text_proj([cfg["tts_pad_token_id"]])
+
+        def prepare(r):
+            vcp = r.voice_clone_prompt
+            refs = vcp.get("ref_code") if vcp is not None else None
+            if refs is not None and any(x is not None for x in refs):
+                raise NotImplementedError("serve_live() with voice-clone reference codes (ICL): use stream(), or "
+                                          "x-vector-only prompts")
+            if r.open_text and r.non_streaming_mode:
+                raise ValueError("open_text needs non_streaming_mode=False: non-streaming mode puts the whole text "
+                                 "into the prefill")
+            if r.open_text and len(r.input_ids) < 4:
+                raise ValueError(f"an open-text head is the three role ids plus at least one text id, got "
+                                 f"{len(r.input_ids)} ids")
+            sp = r.sampling
+            rgp = GenParams(max_new_tokens, one(sp["do_sample"]), one(sp["top_k"]), one(sp["top_p"]),
+                            one(sp["temperature"]), one(sp["subtalker_dosample"]), one(sp["subtalker_top_k"]),
+                            one(sp["subtalker_top_p"]), one(sp["subtalker_temperature"]), eos_token_id,
+                            one(sp["repetition_penalty"]), ignore_eos, one(sp["seed"]))
+            lens = []
+            ins = None if r.instruct_ids is None else [r.instruct_ids]
+            emb, _, trail, _ = self.build_prompts([r.input_ids], [r.language or "auto"], [r.speaker], ins,
+                                                  r.non_streaming_mode, vcp, None, open_text=r.open_text,
+                                                  lens_out=lens)
+            plan = self._prefix_plan(prefix_cache, ins, vcp, lens)
+            return emb[0], trail[0], rgp, plan
+
+        yield from self._serve_codec(
+            self.engine.serve_live_iter(queue, pad, gp, prepare, slots=B, max_prompt=max_prompt, use_graph=use_graph,
+                                        every=every, first=first, text_eos=cfg["tts_eos_token_id"]), B, first, every,
+            fmt)
 
     def _output_format(self, sample_rate, pcm_format):
         """The streams' output format, validated before anything is allocated: None = the codec's own (24 kHz fp32,

@@ -497,6 +497,8 @@ class Session:
         self.busy = False  # held by a live decode_iter (a suspended stream() generator included)
         self.watch = None  # HandoffWatch armed at the last yield of decode_iter
         self.txt = None    # text-append buffers + captured append graph (TalkerEngine.append_text), built on first use
+        self.held = None   # region table + stash of held frames (TalkerEngine._run_frame_held), built on first use
+        self.stashed = 0   # rows whose stash holds their current state (held in the last replay, not refilled since)
         self.cp = CPLane(self, eng)
 
 
@@ -606,6 +608,49 @@ class SlotTable:
         if i >= 0:
             self.slot_p[b] = self.lens[i]
         return i
+
+
+class LiveSlots(SlotTable):
+    """The slot table of a live serving run (serve_live_iter): nothing is known ahead -- requests are admitted to idle
+    rows as they arrive, and a row can be held out of a frame replay.  frames(), capped() and keys() are SlotTable's:
+    a held replay shifts the row's `start` by one, so `frame - start[b]` stays the number of replays the row's request
+    took part in."""
+
+    def __init__(self, slots: int, max_frames: int):
+        self.n, self.B, self.max_frames = 0, int(slots), int(max_frames)
+        self.lens, self.cap = {}, {}                    # request -> prompt length, frame cap
+        self.P = 0
+        self.queue = deque()                            # (unused: the loop keeps the waiting requests themselves)
+        self.req = [-1] * self.B
+        self.start = [0] * self.B
+        self.slot_p = [0] * self.B
+        self.frame = 0
+
+    def admit(self, b: int, i: int, prompt_len: int, cap=None):
+        """Request i starts in idle row b (its single-request prefill is queued before the next replay)."""
+        if self.req[b] >= 0:
+            raise ValueError(f"row {b} is decoding request {self.req[b]}")
+        self.n += 1
+        self.lens[i] = self.slot_p[b] = int(prompt_len)
+        self.cap[i] = self.max_frames if cap is None else min(self.max_frames, int(cap))
+        self.P = max(self.P, int(prompt_len))
+        self.req[b], self.start[b] = int(i), self.frame
+
+    def hold(self, b: int):
+        """Row b is held out of the replay about to be counted (`frame += 1` follows)."""
+        self.start[b] += 1
+
+    def keys(self) -> int:
+        return max((self.slot_p[b] + self.frame - self.start[b] + 1 for b in range(self.B) if self.req[b] >= 0),
+                   default=1)
+
+    def retire(self, b: int) -> int:
+        """Row b's request is over: the row goes idle until the loop admits another."""
+        i = self.req[b]
+        self.lens.pop(i, None)
+        self.cap.pop(i, None)
+        self.start[b], self.req[b] = self.frame, -1
+        return -1
 
 
 class TalkerEngine:
@@ -1316,6 +1361,231 @@ class TalkerEngine:
                         seen[b], fresh[b] = 0, True
                         refill(b)
 
+    # ---------------------------------------------------------------- live serving
+    def serve_live_iter(self, queue, tts_pad, gp: GenParams, prepare, slots: int = 8, max_prompt: int = 512,
+                        use_graph: bool = True, every: int = 8, first: int = 1, text_eos: int = 0):
+        """serve_iter() over an open request stream (TTSModel.serve_live): requests arrive in `queue` (a
+        live.RequestQueue) while the loop runs, an open-text request's text arrives while it decodes, and a row
+        whose next text token has not come is held out of the replays its neighbours take (_run_frame_held) instead of
+        stalling them.  One per-row-parameter session of `slots` rows and K/V capacity `max_prompt`; every request
+        enters through _prefill_slot, a row without one is left as refill() leaves an idle row (a one-position prefill
+        of the pad embedding, finished = 1), so no row ever runs a frame on zeroed counters.
+
+        prepare(request) -> (embeds [P, H], trailing [T, H], the request's GenParams, one-request PrefixPlan or None),
+        called at admission on this thread; what it raises rejects the request (queue.rejected), as does a prompt
+        longer than max_prompt.  Request i draws Philox stream i.
+
+        Yields (session, report) as serve_iter does -- a held row has no new frames and rides along -- and
+        (None, [request ids]) for requests that end without ever decoding (rejected, or cancelled while queued).  A
+        held row's current frame counts as final once one replay has run its code predictor: its 16 codes are
+        complete and its real frame reproduces them; the next cb0 the held replay wrote is not read.  Before each
+        replay the queue is drained; busy open-text rows that are neither closed, capped, nor have the token the
+        replay reads form the hold mask.  When every busy row is held (and each has had its code predictor run) the
+        loop reports what is final, which synchronises and reads the rows' ends, then waits on the queue.  A row
+        starved for queue.timeout seconds, or cancelled, is retired through a report that ends it; the others go on.
+        The loop ends when the queue is closed and drained and every row is idle.  `serve_stats` gains `held`
+        (row-frames held), `admitted` and `retired` (requests that entered / left a row)."""
+        B = int(slots)
+        if not 1 <= B <= 64:
+            raise ValueError(f"serve_live takes 1..64 batch rows, got {slots}")
+        if not gp.per_row:
+            raise ValueError("serve_live_iter needs per-request sampling parameters (a per-row session)")
+        max_frames = max(gp.max_new_tokens - 1, 1)
+        max_prompt, every, first = int(max_prompt), max(1, int(every)), max(1, int(first))
+        tab = LiveSlots(B, max_frames)
+        seed = gp.resolve_seed()
+        eos, H, dev = self.tc["codec_eos_token_id"], self.talker.H, self.dev
+        vocab = self.text_emb.shape[0]
+        stats = {"frames": 0, "slots": B, "requests": 0, "held": 0, "admitted": 0, "retired": 0}
+        self.serve_queued = {}
+        s = self.session(B, max_prompt, max_frames, gp)
+        try:
+            with K.use_workspace(s.ws):
+                pad_row = tts_pad.reshape(1, H).float().to(dev)
+                s.pad_embed.copy_(pad_row.view(-1))
+                s.seed.fill_(seed)
+                s.stashed = 0
+                idle_rec = GenParams(do_sample=False, subtalker_dosample=False).row_records(0, seed)
+                waiting = deque()   # requests received, not in a row yet
+                text = {}           # open-text request not in a row yet -> [ids pushed so far, text closed]
+                where = {}          # request -> its row
+                # per row, TextGate's account: trailing tokens present, (pos, id) not written yet, end of text written
+                n, todo, closed, opened = [0] * B, [deque() for _ in range(B)], [True] * B, [False] * B
+                seen = [0] * B          # frames of the row's request already reported
+                fresh = [True] * B      # the row's request has not been reported yet
+                cp_ran = [False] * B    # the row was held in the last replay: its current frame's codes are complete
+                starved = [None] * B    # host time since which the row has been held
+                kill = [None] * B       # why the row's request is to be retired: "cancel", "timeout", an exception
+                primed = [False] * B    # the row has been prefilled at least once
+                last_report, dirty = 0, False
+
+                def feed(b, ids, close):
+                    for t in ids:
+                        if not 0 <= t < vocab:  # the gather would read outside the embedding table
+                            kill[b] = kill[b] or ValueError(f"text id {t} pushed for request {tab.req[b]} is outside "
+                                                            f"the text vocabulary ({vocab})")
+                            return
+                        if n[b] < max_frames:
+                            todo[b].append((n[b], t))
+                        n[b] += 1
+                    if close and not closed[b]:
+                        if n[b] < max_frames:
+                            todo[b].append((n[b], int(text_eos)))
+                        closed[b] = True
+
+                while True:
+                    new, pushed, text_closed, cancelled, q_closed = queue.drain()
+                    for r in new:
+                        waiting.append(r)
+                        if r.open_text:
+                            text[r.id] = [[], False]
+                    for i, ids in pushed.items():
+                        if i in where:
+                            feed(where[i], ids, False)
+                        elif i in text:
+                            text[i][0].extend(ids)
+                    for i in text_closed:
+                        if i in where:
+                            feed(where[i], [], True)
+                        elif i in text:
+                            text[i][1] = True
+                    notes = []  # requests that end without decoding
+                    for i in cancelled:
+                        if i in where:
+                            kill[where[i]] = kill[where[i]] or "cancel"
+                            continue
+                        for r in [r for r in waiting if r.id == i]:
+                            waiting.remove(r)
+                            text.pop(i, None)
+                            queue.over(i)
+                            stats["requests"] += 1
+                            notes.append(i)
+                    for b in range(B):
+                        while tab.req[b] < 0 and waiting:
+                            r = waiting.popleft()
+                            stats["requests"] += 1
+                            try:
+                                emb, trail, rgp, plan = prepare(r)
+                                P = int(emb.shape[0])
+                                if P > max_prompt:
+                                    raise ValueError(f"prompt of {P} positions exceeds max_prompt ({max_prompt})")
+                                records = rgp.row_records(0, seed)
+                            except Exception as e:  # noqa: BLE001 -- the request is refused, the loop goes on
+                                text.pop(r.id, None)
+                                queue.over(r.id, rejected=e)
+                                notes.append(r.id)
+                                continue
+                            self.serve_queued[r.id] = time.perf_counter()
+                            self._prefill_slot(s, b, (emb, trail), r.id, records, prefix=plan)
+                            tab.admit(b, r.id, P, r.frame_cap)
+                            where[r.id], primed[b] = b, True
+                            seen[b], fresh[b], cp_ran[b], starved[b], kill[b] = 0, True, False, None, None
+                            todo[b].clear()
+                            opened[b], closed[b] = r.open_text, not r.open_text
+                            n[b] = max(len(r.input_ids) - 4, 0) if r.open_text else 0
+                            if r.open_text:
+                                feed(b, *text.pop(r.id))
+                            stats["admitted"] += 1
+                    if notes:
+                        yield None, notes
+                    for b in range(B):
+                        if not primed[b]:  # an idle row decodes one pad position, finished, until a request takes it
+                            self._prefill_slot(s, b, (pad_row, pad_row), 0, idle_rec)
+                            s.finished[b:b + 1].fill_(1)
+                            primed[b] = True
+                    busy = tab.busy()
+                    if not busy:
+                        if waiting:
+                            continue
+                        if q_closed:
+                            break
+                        queue.wait(1.0)
+                        continue
+                    # text a little ahead of the frames, as TextGate.poll writes it
+                    if any(todo[b] and todo[b][0][0] < tab.frames(b) + TextGate.LOW for b in busy):
+                        items = []
+                        for b in busy:
+                            while todo[b] and todo[b][0][0] < tab.frames(b) + TextGate.AHEAD:
+                                items.append((b,) + todo[b].popleft())
+                        self.append_text(s, items, use_graph)
+                    now = time.perf_counter()
+                    held = []
+                    for b in busy:
+                        if (opened[b] and not closed[b] and kill[b] is None and not tab.capped(b)
+                                and n[b] <= tab.frames(b)):
+                            held.append(b)
+                            if starved[b] is None:
+                                starved[b] = now
+                            if cp_ran[b] and now - starved[b] >= queue.timeout:
+                                kill[b] = "timeout"
+                        else:
+                            starved[b] = None
+                    force = any(kill[b] is not None for b in busy)
+                    if not force and (len(held) < len(busy) or any(not cp_ran[b] for b in held)):
+                        mask = sum(1 << b for b in held)
+                        self._run_frame_held(s, min(tab.keys(), s.Lmax), mask, use_graph)
+                        for b in busy:
+                            cp_ran[b] = b in held
+                            if cp_ran[b]:
+                                tab.hold(b)
+                        tab.frame += 1
+                        stats["held"] += len(held)
+                        dirty = True
+                        # (serve_iter's schedule: the codec then sees the feeds serve_stream gives it)
+                        if not (tab.frame - last_report >= every
+                                or any(fresh[b] and tab.frames(b) + cp_ran[b] >= first for b in busy)):
+                            continue
+                    elif not (dirty or force):
+                        # nothing can run and nothing is new: wait for text, a request or a cancel, at most until the
+                        # first starved row's time is up
+                        left = min(starved[b] + queue.timeout - now for b in held)
+                        queue.wait(min(max(left, 0.0), 1.0))
+                        continue
+                    last_report, dirty = tab.frame, False
+                    # frames [0, k_b) of row b are final and column k_b holds its next cb0 (EOS of an ending request);
+                    # a held row's frame k_b is final too, and the column behind it is not read
+                    k = [tab.frames(b) if tab.req[b] >= 0 else 0 for b in range(B)]
+                    c0 = torch.empty(B, max(k) + 1, dtype=torch.int32, pin_memory=True)
+                    c0.copy_(s.codes[:, :max(k) + 1, 0], non_blocking=True)
+                    fw = _flag_word(s)
+                    hf = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+                    if fw is not None:
+                        hf.copy_(fw, non_blocking=True)
+                    torch.cuda.current_stream(self.dev).synchronize()
+                    if int(hf[0]) != 0:  # session-wide and sticky: every request in flight is suspect
+                        _clear_flags(s)
+                        raise HandoffError({tab.req[b] for b in busy}, [r.id for r in waiting])
+                    report, natural = [None] * B, [False] * B
+                    for b in busy:
+                        hit = (c0[b, seen[b]:k[b] + 1] == eos).nonzero()
+                        natural[b] = bool(hit.numel()) or tab.capped(b)
+                        if hit.numel():
+                            f = seen[b] + int(hit[0])
+                        else:
+                            f = k[b] + (1 if cp_ran[b] and not tab.capped(b) else 0)
+                        ended = natural[b] or kill[b] is not None
+                        report[b] = (tab.req[b], seen[b], f, ended, int((c0[b, seen[b]:f] != 0).sum()))
+                        seen[b], fresh[b] = f, False
+                    yield s, report
+                    for b in busy:
+                        if not report[b][3]:
+                            continue
+                        i = tab.req[b]
+                        queue.over(i, timed_out=kill[b] == "timeout" and not natural[b],
+                                   rejected=kill[b] if isinstance(kill[b], BaseException) and not natural[b] else None)
+                        del where[i]
+                        tab.retire(b)
+                        s.finished[b:b + 1].fill_(1)  # idle row: emits EOS until a request takes it
+                        stats["retired"] += 1
+                        todo[b].clear()
+                        opened[b], closed[b], kill[b], starved[b], cp_ran[b] = False, True, None, None, False
+                        seen[b], fresh[b] = 0, True
+                check_handoffs([s])
+        finally:
+            stats["frames"] = tab.frame
+            self.serve_stats = stats
+            self.release([s])
+
     def _prefill_slot(self, s: Session, b: int, req, i: int, records=None, prefix=None):
         """Start a request in batch row b (Philox stream id i): per-row state reset, single-request talker prefill into
         row b's K/V (positions 0..P-1, no left padding), first token (M:1746-1800, 2044).  records: the request's
@@ -1325,6 +1595,7 @@ class TalkerEngine:
         emb, trail = req[0], req[1]
         P, H = int(emb.shape[0]), self.talker.H
         t, dev = self.talker, self.dev
+        s.stashed &= ~(1 << b)
         if P + s.max_frames + 2 > s.Lmax:
             raise ValueError(f"prompt of {P} tokens exceeds the session's K/V capacity ({s.Lmax})")
         for z in (s.seen, s.finished, s.codes):
@@ -1372,6 +1643,7 @@ class TalkerEngine:
         B, P, H = embeds.shape
         dev = self.dev
         s.P = P  # padded prompt length: every row's decode keys are <= P + frames + 1
+        s.stashed = 0
         # reset per-request state
         for z in (s.seen, s.finished, s.codes, s.ctr):
             z.zero_()
@@ -1554,6 +1826,41 @@ class TalkerEngine:
         self._fence_in()
         g.replay()
         self._fence_out()
+
+    def _held_regions(self, s: Session):
+        """What a frame's talk half writes for a row and a later frame of that row reads before rewriting it (DESIGN
+        §19), as qt_row_state regions (tensor at row 0, row stride in bytes, bytes per row): the five counters, tok0,
+        finished, seen, past_hidden, and the row's cb0 embedding -- row 2b + 1 of cp_x and of its bf16 shadow."""
+        B, Hc = s.B, self.cp.H
+        regs = [(s.ctr[f * B:], 4, 4) for f in range(5)]
+        regs += [(s.tok0, 4, 4), (s.finished, 1, 1), (s.seen, s.seen.shape[1], s.seen.shape[1]),
+                 (s.past_hidden, 4 * self.talker.H, 4 * self.talker.H), (s.cp_x[1:], 8 * Hc, 4 * Hc)]
+        if s.cp_x16 is not None:
+            regs.append((s.cp_x16[1:], 4 * Hc, 2 * Hc))
+        return regs
+
+    def _run_frame_held(self, s: Session, keys: int, hold_mask: int, use_graph: bool = True):
+        """_run_frame for a batch some of whose rows must not advance (bit b of hold_mask: row b has no text for this
+        frame, serve_live): the frame itself is the ordinary one -- same graphs, same fence -- and advances every row;
+        the held rows' state is saved in front of it and put back behind it, one qt_row_state launch each, in stream
+        order, outside the captured graph.  A held row thereby re-runs the same frame later: its counters, and with
+        them the Philox keys of its draws, are the same, so it makes the same choices.  What the held frame leaves
+        behind for the row besides the saved set is rewritten by the row's real frame before anything reads it: the
+        K/V at kv_pos, cp_kv, hiddens[b, step + 1], the logits, and codes[b, step + 1, 0] (which the host must not
+        read for a held row); codes[b, step, 1:] are the row's real choices (its code predictor ran on its real state).
+        The save comes before the whole frame, not between its halves: the code-predictor steps reuse cp_x[:B], which
+        overlaps other rows' odd rows.  A row held in consecutive replays is saved once (Session.stashed)."""
+        if not hold_mask:
+            s.stashed = 0
+            return self._run_frame(s, keys, use_graph)
+        if s.B > 64:
+            raise ValueError(f"held frames serve sessions of at most 64 rows, got {s.B}")
+        if s.held is None:
+            s.held = K.RowState(self._held_regions(s), s.B, self.dev)
+        K.row_state(s.held, hold_mask & ~s.stashed, _hip.ROW_SAVE)
+        s.stashed = hold_mask
+        self._run_frame(s, keys, use_graph)
+        K.row_state(s.held, hold_mask, _hip.ROW_RESTORE)
 
     # Frames of concurrent requests on different streams are serialised on the device: each persistent hand-off kernel
     # of a frame (qt_cp_step / qt_cp_prefill, qt_talker_tail, the head-split attention + o_proj) needs all of its 256
