@@ -163,6 +163,22 @@ class RowStateArgs(ctypes.Structure):
                 ("stash", c_void_p), ("stash_row_bytes", c_ll), ("regions", RowRegion * ROW_STATE_MAX_REGIONS)]
 
 
+CODEC_ROW_ADOPT, CODEC_ROW_EXPORT = 0, 1  # QT_CODEC_ROW_*
+CODEC_ROW_MAX_HIST, CODEC_ROW_MAX_LAYERS, CODEC_ROW_MAX_JOBS = 32, 16, 64
+
+
+class CodecRowTable(ctypes.Structure):
+    """qt_codec_row_table: one RowCodecStream slot as qt_codec_row_state sees it"""
+    _fields_ = [("n_hist", c_int), ("n_layers", c_int), ("B", c_int), ("Hkv", c_int), ("Lm", c_int), ("D", c_int),
+                ("window", c_int), ("reserved", c_int), ("nf", c_void_p), ("kv", c_void_p * (2 * CODEC_ROW_MAX_LAYERS)),
+                ("hist", RowRegion * CODEC_ROW_MAX_HIST)]
+
+
+class CodecRowJob(ctypes.Structure):
+    """qt_codec_row_job: one row moved by a qt_codec_row_state call"""
+    _fields_ = [("block", c_void_p), ("row", c_int), ("p", c_int), ("dir", c_int), ("reserved", c_int)]
+
+
 EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_attention", "qt_decode_attention", "qt_decode_attn_ws_bytes",
            "qt_rmsnorm_rec", "qt_small_prefill_attention",
            "qt_decode_attn_oproj", "qt_attn_oproj_ws_bytes", "qt_attn_oproj_resident_blocks",
@@ -172,6 +188,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_sample", "qt_sample_row_bytes", "qt_sample_args_bytes", "qt_rmsnorm", "qt_gather_rows", "qt_frame_embed", "qt_advance", "qt_advance_rows",
            "qt_stream_window", "qt_stream_rows", "qt_trail_append", "qt_kv_prefix",
            "qt_row_state", "qt_row_state_row_bytes",
+           "qt_codec_row_state", "qt_codec_row_state_bytes", "qt_codec_feed_codes",
            "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
@@ -225,6 +242,8 @@ def load_library(path: str = LIB_PATH):
         "qt_trail_append": [P, P, P, c_int, c_int, c_int, c_int, P],
         "qt_kv_prefix": [P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P],
         "qt_row_state": [P, P], "qt_row_state_row_bytes": [P],
+        "qt_codec_row_state": [P, P, c_int, P], "qt_codec_row_state_bytes": [P],
+        "qt_codec_feed_codes": [P, P, P, P, c_int, c_int, c_int, c_int, P, P],
         "qt_stream_window": [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
         "qt_stream_rows": [P, P, c_int, c_int, P, P, P],
         "qt_rvq_gather": [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P],
@@ -255,7 +274,7 @@ def load_library(path: str = LIB_PATH):
     for name, args in sig.items():
         f = getattr(L, name)
         f.argtypes = args
-        f.restype = c_ll if name.endswith(("_ws_bytes", "_row_bytes", "_args_bytes")) else c_int
+        f.restype = c_ll if name.endswith(("_ws_bytes", "_row_bytes", "_args_bytes", "_state_bytes")) else c_int
     return L
 
 

@@ -9,6 +9,7 @@ columns are already the time-interleaved samples: no pixel shuffle pass).
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Dict, List
 
 import torch
@@ -238,6 +239,14 @@ class CodecDecoder:
     def row_stream(self, B: int, max_frames: int, n_max: int = 8) -> "RowCodecStream":
         """stream() with a clock per batch row (rows begin, idle and end independently; feeds of up to n_max frames)."""
         return RowCodecStream(self, B, max_frames, n_max)
+
+    def signature(self):
+        """What a row-state snapshot (RowCodecStream.export_row) and a VoiceCache bind to: this decoder's weights
+        (the object itself), its activation dtype and the geometry of a row's state."""
+        d = self.d
+        return (id(self), str(self.adt), len(self.layers), self.kvh, self.hd, int(d["sliding_window"]), self.lat,
+                int(d["decoder_dim"]), tuple(int(r) for r in d["upsample_rates"]),
+                tuple(int(r) for r in d["upsampling_ratios"]))
 
     def _acquire_slot(self, B, max_frames) -> "_StreamSlot":
         pool = self._slots.setdefault((B, max_frames), [])
@@ -521,6 +530,17 @@ class _RowStreamSlot:
         self.uses = {}
         self.busy = False
         self.ws = K.new_workspace(dev)
+        self.table = None   # kernels.CodecRowTable of this slot (export_row / adopt_rows), built on first use
+
+
+@dataclass
+class CodecRowSnapshot:
+    """One row's incremental-decode state (RowCodecStream.export_row): the packed block of qt_codec_row_state, the
+    row clock p it was taken at, and the signature of the decoder whose state it is."""
+    p: int
+    nbytes: int
+    sig: tuple
+    block: torch.Tensor  # uint8 [nbytes], device
 
 
 class RowCodecStream:
@@ -571,6 +591,79 @@ class RowCodecStream:
             self.close()
         except Exception:
             pass
+
+    # -- row state in and out (the voice cache) ---------------------------------------------
+    def _hist_specs(self):
+        """(stage key, history rows, channels) of every history _compute keeps, in its order."""
+        dec = self.dec
+        taps = lambda Wt: (Wt.taps - 1) * getattr(Wt, "dil", 1)  # noqa: E731
+        specs = [("pre", taps(dec.pre_conv), dec.proj_first.N)]
+        specs += [(f"dw{i}", u["dw_w"].shape[1] - 1, dec.lat) for i, u in enumerate(dec.ups)]
+        specs.append(("conv0", taps(dec.conv0), dec.lat))
+        C = dec.d["decoder_dim"]
+        for bi, blk in enumerate(dec.blocks):
+            specs.append((f"t{bi}", 1, C))
+            C = blk["cout"]
+            for ui, un in enumerate(blk["units"]):
+                specs += [(f"u{bi}.{ui}", taps(un["c1"]), C), (f"v{bi}.{ui}", taps(un["c2"]), C)]
+        specs.append(("last", taps(dec.conv_last), C))
+        return [sp for sp in specs if sp[1] > 0]  # (a 1-tap conv keeps no history)
+
+    def _state_table(self):
+        """The slot's qt_codec_row_state table, built once per slot.  The histories are created lazily by the first
+        feed: they are created here first (zeros, as that feed would), so a fresh slot can adopt."""
+        sl, dec, B = self.slot, self.dec, self.B
+        if sl.table is None:
+            specs = self._hist_specs()
+            for key, H, C in specs:
+                if key not in sl.hist:
+                    sl.hist[key] = torch.zeros(B, H, C, dtype=dec.adt, device=dec.dev)
+            if sorted(sl.hist) != sorted(k for k, _, _ in specs) or \
+                    any(tuple(sl.hist[k].shape) != (B, H, C) or sl.hist[k].dtype != dec.adt for k, H, C in specs):
+                raise RuntimeError("RowCodecStream: the slot's histories are not those of _hist_specs()")
+            sl.table = K.CodecRowTable([sl.hist[k] for k, _, _ in specs], sl.kc, sl.vc, sl.nf_dev,
+                                       dec.d["sliding_window"])
+        return sl.table
+
+    def snapshot_bytes(self) -> int:
+        return self._state_table().block_bytes
+
+    def export_row(self, b: int) -> CodecRowSnapshot:
+        """The complete state of row b (which has begun on this stream) as a snapshot: one launch on the current
+        stream.  The row goes on unchanged."""
+        if not 0 <= b < self.B or not self.live[b]:
+            raise ValueError(f"row {b} has not begun on this stream: nothing to export")
+        tab = self._state_table()
+        block = torch.zeros(tab.block_bytes, dtype=torch.uint8, device=self.dec.dev)
+        K.codec_row_state(tab, [(block, b, self.nf[b], _hip.CODEC_ROW_EXPORT)])
+        return CodecRowSnapshot(self.nf[b], tab.block_bytes, self.dec.signature(), block)
+
+    def adopt_row(self, b: int, snapshot: CodecRowSnapshot):
+        self.adopt_rows([(b, snapshot)])
+
+    def adopt_rows(self, pairs):
+        """Put snapshots into rows -- pairs = [(row, snapshot)], all in one launch on the current stream.  Each row
+        becomes a continuing row at the snapshot's clock p, whatever it held: its spurious head rows were masked in
+        the feed that began it on the exporting stream, so the next feed's valid samples are [0, 1920 nrow), the
+        first 555 of which belong to the frame before p."""
+        jobs = []
+        for b, sn in pairs:
+            if not isinstance(sn, CodecRowSnapshot) or sn.sig != self.dec.signature():
+                raise ValueError("the snapshot is another decoder's row state (weights, dtype or geometry differ)")
+            if not 0 <= b < self.B:
+                raise ValueError(f"row {b} outside [0, {self.B})")
+            if not 1 <= sn.p <= self.max_frames:
+                raise ValueError(f"a snapshot at clock {sn.p} does not fit a stream of {self.max_frames} frames per "
+                                 "row (a row's state begins with its first frame)")
+            jobs.append((sn.block, b, sn.p, _hip.CODEC_ROW_ADOPT))
+        if len({j[1] for j in jobs}) != len(jobs):
+            raise ValueError("two snapshots for one row")
+        tab = self._state_table()
+        if any(sn.nbytes != tab.block_bytes for _, sn in pairs):
+            raise ValueError("the snapshot's size is not this decoder's")
+        K.codec_row_state(tab, jobs)
+        for b, sn in pairs:
+            self.nf[b], self.live[b] = sn.p, True
 
     # -- stages ----------------------------------------------------------------------------------------
     def _window(self, key, x, L, C, H, rpf, head):

@@ -322,21 +322,24 @@ class Qwen3TTSModel:
     @torch.no_grad()
     def stream_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False,
                            voice_clone_prompt=None, non_streaming_mode=False, first_chunk_frames=1, chunk_frames=48,
-                           sample_rate=None, pcm_format="f32", **kwargs):
+                           sample_rate=None, pcm_format="f32", max_batch=None, voice_cache=None, **kwargs):
         """New surface (no reference counterpart, SURVEY.md §8f-1 + 8f-2): streaming voice clone.  Same inputs as
         generate_voice_clone (reference audio is encoded / x-vectored at submit); yields (utterance index, pcm chunk
         np.float32, sample rate, is_last).  Per utterance the chunks concatenate to generate_voice_clone()'s PCM: in
         ICL mode the reference codes are decoded in front of the generated ones and the output starts at their
         boundary -- the wrapper's proportional cut keeps floor(555 R / T) more samples of the reference's tail, a
         length-dependent point a stream cannot know in advance (TTSModel._stream_stateful).  sample_rate /
-        pcm_format: as in stream()."""
+        pcm_format: as in stream().  max_batch: with more texts than max_batch, stream them by continuous batching
+        through max_batch rows (TTSModel.serve_stream); ICL prompts then need voice_cache, a qwen_tts.VoiceCache that
+        keeps each voice's codec state across requests (VoiceCache.warm fills it ahead of the first request)."""
         sr = self._output_format(sample_rate, pcm_format)
         input_ids, ref_ids, vcp, languages = self._voice_clone_inputs(text, language, ref_audio, ref_text,
                                                                       x_vector_only_mode, voice_clone_prompt)
         for i, pcm, last in self.model.stream(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp,
                                               languages=languages, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
-                                              sample_rate=sample_rate, pcm_format=pcm_format,
+                                              sample_rate=sample_rate, pcm_format=pcm_format, max_batch=max_batch,
+                                              voice_cache=voice_cache,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, (pcm if pcm.dtype == torch.int16 else pcm.to(torch.float32)).cpu().numpy(), sr, last
 

@@ -583,6 +583,66 @@ def row_state(rs: RowState, mask: int, direction: int):
     check(_hip.lib().qt_row_state(ctypes.byref(rs.args), stream()), "qt_row_state")
 
 
+class CodecRowTable:
+    """The slot table of qt_codec_row_state: hist = [history tensors [B][H][C]] in a fixed order, kc / vc the layers'
+    fp32 [B][Hkv][Lm][D] caches, nf the int32 [B] row clocks, window the attention's sliding window.  The tensors are
+    kept alive with the table.  block_bytes: the size of a snapshot block."""
+
+    def __init__(self, hist, kc, vc, nf, window: int):
+        self.keep = (list(hist), list(kc), list(vc), nf)
+        t = self.args = _hip.CodecRowTable()
+        t.n_hist, t.n_layers = len(hist), len(kc)
+        if t.n_hist > _hip.CODEC_ROW_MAX_HIST or t.n_layers > _hip.CODEC_ROW_MAX_LAYERS:
+            raise ValueError(f"qt_codec_row_state takes {_hip.CODEC_ROW_MAX_HIST} histories and "
+                             f"{_hip.CODEC_ROW_MAX_LAYERS} layers, got {t.n_hist} and {t.n_layers}")
+        t.B, t.Hkv, t.Lm, t.D = kc[0].shape
+        t.window, t.nf = int(window), ptr(nf)
+        for i, c in enumerate(list(kc) + list(vc)):
+            if c.dtype != torch.float32 or not c.is_contiguous() or tuple(c.shape) != tuple(kc[0].shape):
+                raise ValueError("qt_codec_row_state: the caches are contiguous fp32 [B][Hkv][Lm][D] tensors")
+            t.kv[i] = ptr(c)
+        for r, h in enumerate(hist):
+            if not h.is_contiguous() or h.shape[0] != t.B:
+                raise ValueError("qt_codec_row_state: a history is a contiguous [B][H][C] tensor")
+            per = h[0].numel() * h.element_size()
+            t.hist[r] = _hip.RowRegion(ptr(h), per, per)
+        self.block_bytes = int(_hip.lib().qt_codec_row_state_bytes(ctypes.byref(t)))
+        check(min(self.block_bytes, 0), "qt_codec_row_state_bytes")
+
+
+def codec_row_state(table: CodecRowTable, jobs):
+    """One qt_codec_row_state launch on the current stream for jobs = [(block, row, p, dir)]: dir
+    _hip.CODEC_ROW_EXPORT packs row `row`'s state at clock p into the uint8 block, _hip.CODEC_ROW_ADOPT unpacks a
+    block into the row and sets its device clock to p.  The library checks everything before it launches."""
+    J = len(jobs)
+    if J == 0:
+        return
+    tab = (_hip.CodecRowJob * J)()
+    for j, (block, row, p, d) in enumerate(jobs):
+        if block is not None and (block.dtype != torch.uint8 or block.numel() < table.block_bytes
+                                  or not block.is_contiguous()):
+            raise ValueError(f"codec_row_state job {j}: the block is not a contiguous uint8 tensor of "
+                             f"{table.block_bytes} bytes")
+        tab[j] = _hip.CodecRowJob(ptr(block), int(row), int(p), int(d), 0)
+    check(_hip.lib().qt_codec_row_state(ctypes.byref(table.args), tab, J, stream()), "qt_codec_row_state")
+
+
+def codec_feed_codes(pos, refs, ref_len, codes, out):
+    """out [B][n][Q] = the codes at joint positions pos [B][n] (int32, < 0: zeros) of every row's sequence
+    reference_b + codes[b]: refs an int64 [B] device table of pointers to int32 [R_b][Q] (0: no reference), ref_len
+    int32 [B], codes int32 [B][F][Q]."""
+    B, n = pos.shape
+    F, Q = codes.shape[1], codes.shape[2]
+    if pos.dtype != torch.int32 or codes.dtype != torch.int32 or out.dtype != torch.int32 or \
+            refs.dtype != torch.int64 or ref_len.dtype != torch.int32 or tuple(out.shape) != (B, n, Q) or \
+            codes.shape[0] != B or refs.numel() != B or ref_len.numel() != B or \
+            not (pos.is_contiguous() and codes.is_contiguous() and out.is_contiguous()):
+        raise ValueError("codec_feed_codes: pos int32 [B][n], refs int64 [B], ref_len int32 [B], codes int32 "
+                         "[B][F][Q], out int32 [B][n][Q], all contiguous")
+    check(_hip.lib().qt_codec_feed_codes(ptr(pos), ptr(refs), ptr(ref_len), ptr(codes), B, n, F, Q, ptr(out),
+                                         stream()), "qt_codec_feed_codes")
+
+
 def stream_window(hist, x, xin, B, H, n, C, rows_per_frame, head, rows):
     """xin [B][H+n][C] = [hist | x] per the row table rows [2][B] (nrow, begin), then hist = xin[:, m_b:m_b + H]
     (m_b = nrow[b] * rows_per_frame); a beginning row reads zero history and zeros for its first `head` rows."""

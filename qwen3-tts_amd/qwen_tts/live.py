@@ -38,6 +38,7 @@ class LiveRequest:
     open_text: bool = False
     frame_cap: Optional[int] = None
     sampling: dict = field(default_factory=dict)
+    ref_ids: Optional[List[int]] = None  # a voice-clone (ICL) request's reference text (serve_live(voice_cache=...))
 
 
 class RequestQueue:
@@ -75,10 +76,12 @@ class RequestQueue:
 
     # ------------------------------------------------------------------ producers (any thread)
     def submit(self, input_ids, *, instruct_ids=None, language=None, speaker=None, voice_clone_prompt=None,
-               non_streaming_mode=False, open_text=False, frame_cap=None, **sampling) -> int:
+               non_streaming_mode=False, open_text=False, frame_cap=None, ref_ids=None, **sampling) -> int:
         """Queue a request; returns its id.  **sampling: the per-request sampling parameters of generate() (do_sample,
         top_k, top_p, temperature, the four subtalker_* values, repetition_penalty, seed).  What the loop finds
-        unservable when it assembles the prompt (prompt too long, unknown speaker, ...) ends up in `rejected`."""
+        unservable when it assembles the prompt (prompt too long, unknown speaker, ...) ends up in `rejected`.
+        ref_ids: the reference text's ids of a voice-clone request in ICL mode (its voice_clone_prompt carries
+        reference codes), as generate() takes them; the loop serves such a request when it was given a voice_cache."""
         unknown = set(sampling) - set(SAMPLING_DEFAULTS)
         if unknown:
             raise TypeError(f"submit() got unexpected keyword arguments {sorted(unknown)}")
@@ -86,6 +89,7 @@ class RequestQueue:
             raise ValueError(f"frame_cap must be >= 1, got {frame_cap}")
         ids = _id_list(input_ids)
         ins = None if instruct_ids is None else _id_list(instruct_ids)
+        ref = None if ref_ids is None else _id_list(ref_ids)
         with self._cv:
             if self._closed:
                 raise ValueError("RequestQueue is closed: no submit after close")
@@ -93,7 +97,7 @@ class RequestQueue:
             self._next += 1
             self._new.append(LiveRequest(i, ids, ins, language, speaker, voice_clone_prompt, bool(non_streaming_mode),
                                          bool(open_text), None if frame_cap is None else int(frame_cap),
-                                         {**SAMPLING_DEFAULTS, **sampling}))
+                                         {**SAMPLING_DEFAULTS, **sampling}, ref))
             self._live.add(i)
             if open_text:
                 self._open[i] = True

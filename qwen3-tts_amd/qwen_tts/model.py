@@ -14,6 +14,7 @@ from . import kernels as K
 from .prefix import PrefixCache, PrefixPlan
 from .resample import PcmResampler, output_format
 from .talker import MIN_NEW_TOKENS, GenParams, HandoffWatch, TalkerEngine
+from .voice import VoiceCache, boundary_skip, check_codes, joint_walk, plan_feed
 
 
 class _Runs:
@@ -320,6 +321,18 @@ class TTSModel:
             return None  # nobody takes part: the call runs exactly the code it runs without a cache
         return PrefixPlan(prefix_cache, keys, lens)
 
+    # -------------------------------------------------------------------------------- voice cache
+    def _voice_bind(self, voice_cache):
+        """Check a call's voice_cache= before anything is allocated, and bind it to the codec decoder."""
+        if voice_cache is None:
+            return None
+        if not isinstance(voice_cache, VoiceCache):
+            raise ValueError(f"voice_cache must be a qwen_tts.VoiceCache, got {type(voice_cache).__name__}")
+        if self.speech_tokenizer is None:
+            raise ValueError("voice_cache needs the speech tokenizer: load_speech_tokenizer() first")
+        voice_cache.bind(self.speech_tokenizer.model)
+        return voice_cache
+
     # -------------------------------------------------------------------------------- generate
     @torch.no_grad()
     def generate(self, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None, languages=None,
@@ -390,7 +403,7 @@ class TTSModel:
                temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
                first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None,
-               text_feed=None, sample_rate=None, pcm_format="f32", prefix_cache=None, **kwargs):
+               text_feed=None, sample_rate=None, pcm_format="f32", prefix_cache=None, voice_cache=None, **kwargs):
         """Streaming generation (the reference has none): yields (row, pcm, last) as frames finish.
 
         Per row the chunks concatenate to the one-shot generate() + decode() PCM (Z:259-365): the reference
@@ -424,8 +437,12 @@ class TTSModel:
         input samples' worth) follow with the next chunk; last=True flushes, so the last chunk may hold samples where
         the default's is empty.  The stateless left_context form serves the default format only.
 
-        prefix_cache: as in generate() -- with text_feed and with max_batch too."""
+        prefix_cache: as in generate() -- with text_feed and with max_batch too.
+
+        voice_cache: a qwen_tts.VoiceCache, used when max_batch routes the call to serve_stream(), which
+        then serves voice-clone prompts with reference codes too; the other routes decode the reference themselves."""
         fmt = self._output_format(sample_rate, pcm_format)
+        self._voice_bind(voice_cache)
         lens = self._prefix_bind(prefix_cache)
         if fmt is not None and left_context is not None:
             raise NotImplementedError("stream(left_context=...) with sample_rate / pcm_format: use the default "
@@ -448,7 +465,7 @@ class TTSModel:
                 subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed,
                 max_batch=max_batch, first_chunk_frames=first_chunk_frames,
                 chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, sample_rate=sample_rate,
-                pcm_format=pcm_format, prefix_cache=prefix_cache, **kwargs)
+                pcm_format=pcm_format, prefix_cache=prefix_cache, voice_cache=voice_cache, **kwargs)
             return
         dec = self.speech_tokenizer.model
         up = dec.total_upsample
@@ -584,7 +601,8 @@ class TTSModel:
                      top_p=1.0, temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                      subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False,
                      seed=None, max_batch=8, first_chunk_frames=1, chunk_frames=8, use_graph=True, philox_ids=None,
-                     frame_caps=None, sample_rate=None, pcm_format="f32", prefix_cache=None, **kwargs):
+                     frame_caps=None, sample_rate=None, pcm_format="f32", prefix_cache=None, voice_cache=None,
+                     **kwargs):
         """Streaming from the continuously batched route (the reference has neither): the requests are
         decoded through max_batch batch rows as generate(max_batch=...) decodes them, and each request's audio
         leaves as it is generated -- yields (request index, pcm, last).
@@ -599,10 +617,18 @@ class TTSModel:
         while the other rows carry on.  The sampling parameters take per-request lists as in generate().  Voice-clone
         prompts that carry reference codes (ICL) are not supported here; x-vector-only prompts are.
         sample_rate / pcm_format: as in stream() -- one resampler launch per codec feed for all slots, a slot's state
-        reset when its request changes.  prefix_cache: as in generate() -- the first prefill and every refill use it."""
+        reset when its request changes.  prefix_cache: as in generate() -- the first prefill and every refill use it.
+
+        voice_cache: a qwen_tts.VoiceCache.  With one, prompts whose ref_code[i] is not None (ICL) are
+        served too, mixed freely with x-vector-only and plain requests: request i's audio is the decode of
+        cat(ref_i, codes_i) from sample 1920 R_i on, up to 1920 x #nonzero-cb0 of both (the rule _stream_stateful
+        documents, its up-to-555-sample deviation from the wrapper's proportional cut included).  The row adopts the
+        codec state behind the voice's reference frames from the cache (built on a miss on a one-row stream of its
+        own), so a request's first chunk is 1920 x first_chunk_frames - 555 samples as for any other request."""
         fmt = self._output_format(sample_rate, pcm_format)
+        voice = self._voice_bind(voice_cache)
         refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
-        if refs is not None and any(r is not None for r in refs):
+        if voice is None and refs is not None and any(r is not None for r in refs):
             raise NotImplementedError("serve_stream() / stream(max_batch=...) with voice-clone reference codes (ICL): "
                                       "use stream() without max_batch, or x-vector-only prompts")
         lens = self._prefix_bind(prefix_cache)
@@ -620,12 +646,18 @@ class TTSModel:
         first, every = max(1, int(first_chunk_frames)), max(1, int(chunk_frames))
         yield from self._serve_codec(
             self.engine.serve_iter(reqs, pad, gp, slots=B, use_graph=use_graph, every=every, first=first,
-                                   philox_ids=philox_ids, prefix=plan), B, first, every, fmt)
+                                   philox_ids=philox_ids, prefix=plan), B, first, every, fmt, voice,
+            None if refs is None else (lambda i: refs[i]))
 
-    def _serve_codec(self, reports, B, first, every, fmt):
+    def _serve_codec(self, reports, B, first, every, fmt, voice=None, ref_of=None):
         """The codec half of serve_stream() and serve_live(): consumes the talker's (session, report) items
         (TalkerEngine.serve_iter / serve_live_iter) and yields (request, pcm, last).  A row without new frames in a
-        report -- idle, or held -- rides along.  An item (None, [requests]) names requests that end without audio."""
+        report -- idle, or held -- rides along.  An item (None, [requests]) names requests that end without audio.
+        voice (a VoiceCache) selects the route that also serves requests with reference codes, ref_of(request) ->
+        its reference codes or None (_serve_codec_voice)."""
+        if voice is not None:
+            yield from self._serve_codec_voice(reports, B, first, every, fmt, voice, ref_of)
+            return
         dec = self.speech_tokenizer.model
         up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
         caps = sorted({first, every})  # feed capacities (one captured codec graph each)
@@ -655,12 +687,9 @@ class TTSModel:
                         if out is not None:
                             out.reset(b)
                     nz[b] += nzb
-                    for t in range(lo, f):
-                        if t % RC == 0:  # frame t opens a reference chunk: begin, after chunk 0 on the 25 context frames
-                            ctx = RX if t else 0
-                            marks[b][len(todo[b])] = ctx * up
-                            todo[b] += range(t - ctx, t)
-                        todo[b].append(t)
+                    # a frame that opens a reference chunk begins the row, after chunk 0 on the 25 context frames
+                    todo[b], mk = joint_walk(0, lo, f, RC, RX)
+                    marks[b] = {k: c * up for k, c in mk.items()}
                     if ended[b] and not todo[b]:  # nothing new: the request's audio was complete already
                         if out is not None:  # what the filter still holds back
                             yield i, out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b], True
@@ -669,11 +698,8 @@ class TTSModel:
                 at = [0] * B
                 while any(at[b] < len(todo[b]) for b in range(B)):
                     nrow, begin = [0] * B, [0] * B
-                    for b in range(B):
-                        hi = min(len(todo[b]), at[b] + caps[-1])
-                        nxt = [m for m in marks[b] if at[b] < m < hi]  # a restart opens a feed of its own
-                        nrow[b] = (min(nxt) if nxt else hi) - at[b]
-                        begin[b] = int(nrow[b] > 0 and at[b] in marks[b])
+                    for b in range(B):  # (a restart opens a feed of its own)
+                        nrow[b], begin[b] = plan_feed(todo[b], marks[b], at[b], caps[-1])
                     n = next(c for c in caps if c >= max(nrow))
                     ix = torch.tensor([todo[b][at[b]:at[b] + nrow[b]] + [0] * (n - nrow[b]) for b in range(B)],
                                       dtype=torch.long).pin_memory().to(dev, non_blocking=True)
@@ -704,10 +730,122 @@ class TTSModel:
             rs.close()
             reports.close()
 
+    def _serve_codec_voice(self, reports, B, first, every, fmt, voice, ref_of):
+        """_serve_codec for calls with a VoiceCache: requests with reference codes are served beside the
+        others.  Request i decodes cat(ref_i, codes_i): its generated frame t sits at joint position R_i + t, and the
+        chunk walk (voice.joint_walk), the restarts and the 1920 x #nonzero-cb0 length rule run over joint positions.
+        In the first report of its slot the request's voice entry is looked up or built (VoiceCache.get: on a miss
+        the reference frames are decoded on a one-row stream of their own, never through this stream's feeds), and
+        the row adopts the entry's state -- all rows adopting in that report in one qt_codec_row_state launch.  The
+        code window of every feed is assembled on the device from the joint positions (qt_codec_feed_codes), so a
+        restart's 25 context frames come from reference and / or generated frames alike."""
+        dec = self.speech_tokenizer.model
+        up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
+        caps = sorted({first, every})  # feed capacities (one captured codec graph each)
+        dev = self.device
+        rs = dec.row_stream(B, RX + RC, caps[-1])
+        out = None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, dev)
+        req = [-1] * B        # request in each slot, as the codec has seen it
+        discard = [0] * B     # samples of the slot's decode still to drop (a restarted chunk's context, the boundary)
+        extra = [0] * B       # ... to drop on top of the context's at the request's first begin (R a chunk multiple)
+        cum = [0] * B         # sample of the request's whole decode the slot has reached (1920 R at its start)
+        nz = [0] * B          # nonzero cb0 among the request's reference and final frames
+        Rb = [0] * B          # reference frames of the slot's request
+        held = [None] * B     # the slot's voice entry (keeps its reference codes alive while the row reads them)
+        # per-slot reference table of qt_codec_feed_codes: pointers and lengths, re-uploaded when a slot's request
+        # changes; the joint positions of a feed go up from pinned memory in stream order
+        ref_ptr = torch.zeros(B, dtype=torch.int64, device=dev)
+        ref_len = torch.zeros(B, dtype=torch.int32, device=dev)
+        empty = torch.int16 if fmt is not None and fmt[1] == "s16" else torch.float32
+        try:
+            for s, report in reports:
+                if s is None:
+                    for i in report:
+                        if ref_of is not None:
+                            ref_of(i)  # (a live loop forgets the request's reference)
+                        yield i, torch.zeros(0, dtype=empty, device=dev), True
+                    continue
+                # per slot: the joint positions to feed, and the positions in that list at which the row (re)starts
+                todo, marks, ended = [[] for _ in range(B)], [{} for _ in range(B)], [False] * B
+                adopt, changed = [], False
+                for b, r in enumerate(report):
+                    if r is None:
+                        continue
+                    i, lo, f, ended[b], nzb = r
+                    if req[b] != i:
+                        req[b], discard[b], extra[b], cum[b], nz[b], Rb[b], held[b] = i, 0, 0, 0, 0, 0, None
+                        if out is not None:
+                            out.reset(b)
+                        ref = None if ref_of is None else ref_of(i)
+                        if ref is not None and len(ref) > 0:
+                            e = held[b] = voice.get(dec, ref)
+                            Rb[b], nz[b], cum[b] = e.R, e.nz, up * e.R
+                            takes, skip = boundary_skip(e.R, RC)
+                            if takes:
+                                adopt.append((b, e))
+                                discard[b] = skip
+                            else:
+                                extra[b] = skip
+                        changed = True
+                    nz[b] += nzb
+                    todo[b], mk = joint_walk(Rb[b], lo, f, RC, RX)
+                    marks[b] = {k: c * up for k, c in mk.items()}
+                    if ended[b] and not todo[b]:  # nothing new: the request's audio was complete already
+                        if out is not None:  # what the filter still holds back
+                            yield i, out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b], True
+                            continue
+                        yield i, torch.zeros(0, device=dev), True
+                if changed:
+                    tab = [[0 if held[b] is None else held[b].ref.data_ptr() for b in range(B)], Rb]
+                    ref_ptr.copy_(torch.tensor(tab[0], dtype=torch.int64).pin_memory(), non_blocking=True)
+                    ref_len.copy_(torch.tensor(tab[1], dtype=torch.int32).pin_memory(), non_blocking=True)
+                if adopt:
+                    main = torch.cuda.current_stream(dev)
+                    for _, e in adopt:
+                        if e.event is not None:
+                            main.wait_event(e.event)
+                    rs.adopt_rows([(b, e.snapshot) for b, e in adopt])
+                at = [0] * B
+                while any(at[b] < len(todo[b]) for b in range(B)):
+                    nrow, begin = [0] * B, [0] * B
+                    for b in range(B):  # (a restart opens a feed of its own)
+                        nrow[b], begin[b] = plan_feed(todo[b], marks[b], at[b], caps[-1])
+                    n = next(c for c in caps if c >= max(nrow))
+                    pos = torch.tensor([todo[b][at[b]:at[b] + nrow[b]] + [-1] * (n - nrow[b]) for b in range(B)],
+                                       dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+                    win = torch.empty(B, n, s.codes.shape[2], dtype=torch.int32, device=dev)
+                    K.codec_feed_codes(pos, ref_ptr, ref_len, s.codes, win)
+                    pcm = rs.feed(win, nrow, begin)
+                    pend = []  # (slot, first sample, samples, last) of this feed, for the resampler's one launch
+                    for b in range(B):
+                        if not nrow[b]:
+                            continue
+                        if begin[b]:
+                            discard[b], extra[b] = marks[b][at[b]] + extra[b], 0
+                        at[b] += nrow[b]
+                        lo_s, hi_s = 555 if begin[b] else 0, up * nrow[b]
+                        d = min(discard[b], hi_s - lo_s)
+                        discard[b] -= d
+                        lo_s += d
+                        last = ended[b] and at[b] == len(todo[b])
+                        if ended[b]:  # the reference's length rule: 1920 x #nonzero cb0 of the whole sequence
+                            hi_s = min(hi_s, lo_s + max(up * nz[b] - cum[b], 0))
+                        if hi_s > lo_s or last:
+                            cum[b] += hi_s - lo_s
+                            if out is not None:
+                                pend.append((b, lo_s, hi_s - lo_s, last))
+                                continue
+                            yield req[b], pcm[b, lo_s:hi_s].clone(), last
+                    if pend:
+                        yield from self._resampled(out, pcm, pend, req)
+        finally:
+            rs.close()
+            reports.close()
+
     @torch.no_grad()
     def serve_live(self, queue, max_batch=8, max_prompt=512, max_new_tokens=4096, eos_token_id=None, ignore_eos=False,
                    seed=None, first_chunk_frames=1, chunk_frames=8, use_graph=True, sample_rate=None, pcm_format="f32",
-                   prefix_cache=None):
+                   prefix_cache=None, voice_cache=None):
         """Live serving (the reference has none): serve_stream() over an open request stream.  `queue` is
         a qwen_tts.RequestQueue; requests are submitted to it while this generator runs, each with its own sampling
         parameters, and decoded through max_batch batch rows as they arrive -- yields (request id, pcm, last).
@@ -725,11 +863,15 @@ class TTSModel:
 
         Only the thread running this generator issues GPU work, prompt assembly included (at admission).  max_prompt:
         the K/V capacity per row in prompt positions.  seed: the call's seed, for requests that name none; request i
-        draws Philox stream i.  sample_rate / pcm_format / prefix_cache: as in serve_stream()."""
+        draws Philox stream i.  sample_rate / pcm_format / prefix_cache / voice_cache: as in serve_stream() -- with a
+        voice_cache, a request submitted with reference codes (and its reference text: submit(..., ref_ids=...)) is
+        served; without one it stays a rejection."""
         from .live import RequestQueue
         if not isinstance(queue, RequestQueue):
             raise ValueError(f"queue must be a qwen_tts.RequestQueue, got {type(queue).__name__}")
         fmt = self._output_format(sample_rate, pcm_format)
+        voice = self._voice_bind(voice_cache)
+        live_refs = {}  # request -> its reference codes, from admission until the codec half has taken them
         self._prefix_bind(prefix_cache)
         B = int(max_batch)
         if not 1 <= B <= 64:
@@ -744,9 +886,16 @@ class TTSModel:
         def prepare(r):
             vcp = r.voice_clone_prompt
             refs = vcp.get("ref_code") if vcp is not None else None
-            if refs is not None and any(x is not None for x in refs):
+            icl = refs is not None and any(x is not None for x in refs)
+            if icl and voice is None:
                 raise NotImplementedError("serve_live() with voice-clone reference codes (ICL): use stream(), or "
                                           "x-vector-only prompts")
+            if vcp is not None and any(vcp.get("icl_mode") or []) and (not icl or r.ref_ids is None):
+                raise ValueError("a voice-clone request in icl_mode needs its reference codes and the reference "
+                                 "text's ids: submit(..., voice_clone_prompt=..., ref_ids=...)")
+            if icl and r.open_text:
+                raise NotImplementedError("open_text with voice-clone reference codes (ICL): the reference text and "
+                                          "codes take the text's place in the prefill")
             if r.open_text and r.non_streaming_mode:
                 raise ValueError("open_text needs non_streaming_mode=False: non-streaming mode puts the whole text "
                                  "into the prefill")
@@ -761,15 +910,19 @@ class TTSModel:
             lens = []
             ins = None if r.instruct_ids is None else [r.instruct_ids]
             emb, _, trail, _ = self.build_prompts([r.input_ids], [r.language or "auto"], [r.speaker], ins,
-                                                  r.non_streaming_mode, vcp, None, open_text=r.open_text,
-                                                  lens_out=lens)
+                                                  r.non_streaming_mode, vcp, [r.ref_ids] if icl else None,
+                                                  open_text=r.open_text, lens_out=lens)
             plan = self._prefix_plan(prefix_cache, ins, vcp, lens)
+            if icl:
+                # (a malformed reference rejects the request here, not in the loop)
+                check_codes(self.speech_tokenizer.model, VoiceCache.codes_array(refs[0]))
+                live_refs[r.id] = refs[0]
             return emb[0], trail[0], rgp, plan
 
         yield from self._serve_codec(
             self.engine.serve_live_iter(queue, pad, gp, prepare, slots=B, max_prompt=max_prompt, use_graph=use_graph,
                                         every=every, first=first, text_eos=cfg["tts_eos_token_id"]), B, first, every,
-            fmt)
+            fmt, voice, lambda i: live_refs.pop(i, None))
 
     def _output_format(self, sample_rate, pcm_format):
         """The streams' output format, validated before anything is allocated: None = the codec's own (24 kHz fp32,
