@@ -141,6 +141,19 @@ class ResampleArgs(ctypes.Structure):
                 ("B", c_int), ("reserved", c_int), ("table", c_void_p), ("rows", ctypes.POINTER(ResampleRow))]
 
 
+TEMPO_STATE_BYTES = 4104  # QT_TEMPO_STATE_BYTES
+
+
+class TempoRow(ctypes.Structure):
+    """qt_tempo_row: one row of a qt_tempo call (host table)"""
+    _fields_ = [("src", c_void_p), ("out", c_void_p), ("state_in", c_void_p), ("state_out", c_void_p), ("pos", c_ll),
+                ("j0", c_ll), ("block0", c_ll), ("n", c_int), ("count", c_int), ("S", c_int), ("flush", c_int)]
+
+
+class TempoArgs(ctypes.Structure):
+    _fields_ = [("B", c_int), ("reserved", c_int), ("window", c_void_p), ("rows", ctypes.POINTER(TempoRow))]
+
+
 KV_ADOPT, KV_EXPORT = 0, 1  # QT_KV_*
 
 
@@ -189,7 +202,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_stream_window", "qt_stream_rows", "qt_trail_append", "qt_kv_prefix",
            "qt_row_state", "qt_row_state_row_bytes",
            "qt_codec_row_state", "qt_codec_row_state_bytes", "qt_codec_feed_codes",
-           "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample",
+           "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample", "qt_tempo",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
 
@@ -251,6 +264,7 @@ def load_library(path: str = LIB_PATH):
         "qt_dwconv_ln": [P, c_int, c_int, c_int, c_int, P, P, P, P, c_float, P, P],
         "qt_clamp_pcm": [P, c_int, c_ll, P, P],
         "qt_resample": [P, P],
+        "qt_tempo": [P, P],
         "qt_decode_attn_ws_bytes": [c_int, c_int, c_int, c_int, c_int],
         "qt_decode_attn_oproj": [P, P],
         "qt_attn_oproj_ws_bytes": [c_int, c_int],

@@ -18,6 +18,7 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .. import audio as _audio
 from .. import resample as _resample
+from .. import tempo as _tempo
 from ..codec import CodecDecoder
 from ..encoder import TokenizerEncoder, encoder_specs
 from ..weights import codec_specs, is_preset_dir, load_safetensors, read_json, resolve_path, synthetic
@@ -92,11 +93,13 @@ class Qwen3TTSTokenizer:
             return (codes,)
         return EncoderOutput(audio_codes=codes)
 
-    def decode(self, encoded, sample_rate=None, pcm_format="f32", _cut=None) -> Tuple[List[np.ndarray], int]:
+    def decode(self, encoded, sample_rate=None, pcm_format="f32", _cut=None,
+               _steps=None) -> Tuple[List[np.ndarray], int]:
         """Z:259-365.  sample_rate / pcm_format (the reference has neither): the wavs resampled on the
         device before the host copy (qwen_tts.PcmResampler.one_shot), float32 or int16, and the requested rate.
         _cut (generate_voice_clone): per wav None or (R, T), dropping its first int(R / T * len) samples before the
-        resampler sees it."""
+        resampler sees it.  _steps (the generate_* wrappers' speed): per wav its speed step, applied after
+        the cut and before the resampler (qwen_tts.tempo.PcmTempo.one_shot)."""
         fmt = _resample.output_format(sample_rate, pcm_format, self.get_output_sample_rate())
         if hasattr(encoded, "audio_codes"):
             codes_list = encoded.audio_codes
@@ -117,9 +120,15 @@ class Qwen3TTSTokenizer:
             padded = pad_sequence(codes_list, batch_first=True, padding_value=0).to(self.device)
         with torch.inference_mode(), torch.cuda.device(self.device):
             wavs = self.model.decode(padded.long())
-            if fmt is not None:
+            if fmt is not None or _steps is not None:
                 if _cut is not None:
                     wavs = [w if c is None else w[int(c[0] / max(c[1], 1) * w.shape[0]):] for w, c in zip(wavs, _cut)]
+                if _steps is not None:
+                    tp = _tempo.PcmTempo(1, self.device)
+                    wavs = [w.to(torch.float32) if s == 100 else tp.one_shot(w.to(torch.float32), s)
+                            for w, s in zip(wavs, _steps)]
+                if fmt is None:
+                    return [w.cpu().numpy() for w in wavs], self.get_output_sample_rate()
                 x = pad_sequence([w.to(torch.float32) for w in wavs], batch_first=True)
                 rs = _resample.PcmResampler(1, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, self.device)
                 return [w.cpu().numpy() for w in rs.one_shot(x, [int(w.shape[0]) for w in wavs])], fmt[0].sample_rate

@@ -686,6 +686,17 @@ def resample(table, up, down, half, taps, H, pcm_format, rows):
     check(_hip.lib().qt_resample(ctypes.byref(a), stream()), "qt_resample")
 
 
+def tempo(window, rows):
+    """qt_tempo: rows = one (src, out, state_in, state_out, pos, j0, block0, n, count, S, flush) per row, pointers as
+    ints or None (tempo.PcmTempo.push builds them and owns the counters)."""
+    tab = (_hip.TempoRow * len(rows))()
+    for r, (src, out, sin, sout, pos, j0, block0, n, count, S, flush) in zip(tab, rows):
+        r.src, r.out, r.state_in, r.state_out = src, out, sin, sout
+        r.pos, r.j0, r.block0, r.n, r.count, r.S, r.flush = pos, j0, block0, n, count, S, flush
+    a = _hip.TempoArgs(len(rows), 0, ptr(window), tab)
+    check(_hip.lib().qt_tempo(ctypes.byref(a), stream()), "qt_tempo")
+
+
 def rope_tables(head_dim: int, theta: float, npos: int, device):
     """cos/sin [npos][D/2] computed exactly as the reference (fp32 on CPU, M:526-592), then uploaded."""
     inv = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).to(dtype=torch.float) / head_dim))

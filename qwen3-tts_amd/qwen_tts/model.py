@@ -13,6 +13,7 @@ import torch
 from . import kernels as K
 from .prefix import PrefixCache, PrefixPlan
 from .resample import PcmResampler, output_format
+from .tempo import PcmOutput, speed_steps
 from .talker import MIN_NEW_TOKENS, GenParams, HandoffWatch, TalkerEngine
 from .voice import VoiceCache, boundary_skip, check_codes, joint_walk, plan_feed
 
@@ -403,7 +404,8 @@ class TTSModel:
                temperature=0.9, subtalker_dosample=True, subtalker_top_k=50, subtalker_top_p=1.0,
                subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
                first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None,
-               text_feed=None, sample_rate=None, pcm_format="f32", prefix_cache=None, voice_cache=None, **kwargs):
+               text_feed=None, sample_rate=None, pcm_format="f32", prefix_cache=None, voice_cache=None, speed=None,
+               **kwargs):
         """Streaming generation (the reference has none): yields (row, pcm, last) as frames finish.
 
         Per row the chunks concatenate to the one-shot generate() + decode() PCM (Z:259-365): the reference
@@ -440,13 +442,24 @@ class TTSModel:
         prefix_cache: as in generate() -- with text_feed and with max_batch too.
 
         voice_cache: a qwen_tts.VoiceCache, used when max_batch routes the call to serve_stream(), which
-        then serves voice-clone prompts with reference codes too; the other routes decode the reference themselves."""
+        then serves voice-clone prompts with reference codes too; the other routes decode the reference themselves.
+
+        speed: the speaking rate, 0.5 to 2.0 in hundredths -- a number, or one per request.  Each row's
+        default sample sequence goes through the stateful device time-stretch (tempo.PcmTempo, in front of the
+        resampler; one launch per codec report for all rows): the chunks concatenate to PcmTempo.one_shot of the
+        default's, ceil(100 N / S) samples, bit for bit whatever the chunking.  The output for the last 25 to 35 ms
+        of input is held back for the search and follows with the next chunk; last=True flushes.  A request at 1.0
+        keeps the default's bits; with every request at 1.0 (or None) no stage is built.  The stateless left_context
+        form does not serve it."""
         fmt = self._output_format(sample_rate, pcm_format)
+        steps = None if speed is None else speed_steps(speed, 0 if input_ids is None else len(input_ids))
         self._voice_bind(voice_cache)
         lens = self._prefix_bind(prefix_cache)
         if fmt is not None and left_context is not None:
             raise NotImplementedError("stream(left_context=...) with sample_rate / pcm_format: use the default "
                                       "stateful stream")
+        if steps is not None and left_context is not None:
+            raise NotImplementedError("stream(left_context=...) with speed: use the default stateful stream")
         if text_feed is not None:
             yield from self._stream_fed(text_feed, input_ids, instruct_ids, voice_clone_prompt, languages, speakers,
                                         non_streaming_mode, left_context, max_batch, first_chunk_frames, chunk_frames,
@@ -454,7 +467,7 @@ class TTSModel:
                                         GenParams(max_new_tokens, do_sample, top_k, top_p, temperature,
                                                   subtalker_dosample, subtalker_top_k, subtalker_top_p,
                                                   subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos,
-                                                  seed), fmt, prefix_cache)
+                                                  seed), fmt, prefix_cache, steps)
             return
         if max_batch is not None and input_ids is not None and len(input_ids) > int(max_batch):
             if left_context is not None:
@@ -465,7 +478,7 @@ class TTSModel:
                 subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed,
                 max_batch=max_batch, first_chunk_frames=first_chunk_frames,
                 chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, sample_rate=sample_rate,
-                pcm_format=pcm_format, prefix_cache=prefix_cache, voice_cache=voice_cache, **kwargs)
+                pcm_format=pcm_format, prefix_cache=prefix_cache, voice_cache=voice_cache, speed=speed, **kwargs)
             return
         dec = self.speech_tokenizer.model
         up = dec.total_upsample
@@ -500,7 +513,7 @@ class TTSModel:
         # the generation of the next one (~3 ms per frame), so playback started at the first packet never starves
         if left_context is None:
             yield from self._stream_stateful(dec, emb, mask, trail, pad, gp, B, eos, first_chunk_frames, chunk_frames,
-                                             use_graph, prefix, started, fmt=fmt, plan=plan)
+                                             use_graph, prefix, started, fmt=fmt, plan=plan, steps=steps)
             return
         if prefix is not None:
             raise NotImplementedError("stream(left_context=...) with voice-clone reference codes (ICL): use the "
@@ -560,7 +573,7 @@ class TTSModel:
 
     def _stream_fed(self, feed, heads, instruct_ids, voice_clone_prompt, languages, speakers, non_streaming_mode,
                     left_context, max_batch, first_chunk_frames, chunk_frames, use_graph, gp, fmt=None,
-                    prefix_cache=None):
+                    prefix_cache=None, steps=None):
         """stream(text_feed=feed): the combinations it does not serve are refused before anything is allocated."""
         from .feed import TextFeed
         from .talker import TextGate
@@ -593,7 +606,7 @@ class TTSModel:
         gate = TextGate(feed, [len(h) - 4 for h in heads], self.config["tts_eos_token_id"])
         yield from self._stream_stateful(self.speech_tokenizer.model, emb, mask, trail, pad, gp, B,
                                          self.engine.tc["codec_eos_token_id"], first_chunk_frames, chunk_frames,
-                                         use_graph, gate=gate, fmt=fmt, plan=plan)
+                                         use_graph, gate=gate, fmt=fmt, plan=plan, steps=steps)
 
     @torch.no_grad()
     def serve_stream(self, input_ids=None, instruct_ids=None, ref_ids=None, voice_clone_prompt=None, languages=None,
@@ -602,7 +615,7 @@ class TTSModel:
                      subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False,
                      seed=None, max_batch=8, first_chunk_frames=1, chunk_frames=8, use_graph=True, philox_ids=None,
                      frame_caps=None, sample_rate=None, pcm_format="f32", prefix_cache=None, voice_cache=None,
-                     **kwargs):
+                     speed=None, **kwargs):
         """Streaming from the continuously batched route (the reference has neither): the requests are
         decoded through max_batch batch rows as generate(max_batch=...) decodes them, and each request's audio
         leaves as it is generated -- yields (request index, pcm, last).
@@ -618,6 +631,8 @@ class TTSModel:
         prompts that carry reference codes (ICL) are not supported here; x-vector-only prompts are.
         sample_rate / pcm_format: as in stream() -- one resampler launch per codec feed for all slots, a slot's state
         reset when its request changes.  prefix_cache: as in generate() -- the first prefill and every refill use it.
+        speed: as in stream(), a number or one per request -- a slot's tempo state is reset, and takes the new
+        request's rate, when its request changes.
 
         voice_cache: a qwen_tts.VoiceCache.  With one, prompts whose ref_code[i] is not None (ICL) are
         served too, mixed freely with x-vector-only and plain requests: request i's audio is the decode of
@@ -626,6 +641,7 @@ class TTSModel:
         codec state behind the voice's reference frames from the cache (built on a miss on a one-row stream of its
         own), so a request's first chunk is 1920 x first_chunk_frames - 555 samples as for any other request."""
         fmt = self._output_format(sample_rate, pcm_format)
+        steps = None if speed is None else speed_steps(speed, 0 if input_ids is None else len(input_ids))
         voice = self._voice_bind(voice_cache)
         refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
         if voice is None and refs is not None and any(r is not None for r in refs):
@@ -647,16 +663,18 @@ class TTSModel:
         yield from self._serve_codec(
             self.engine.serve_iter(reqs, pad, gp, slots=B, use_graph=use_graph, every=every, first=first,
                                    philox_ids=philox_ids, prefix=plan), B, first, every, fmt, voice,
-            None if refs is None else (lambda i: refs[i]))
+            None if refs is None else (lambda i: refs[i]), None if steps is None else steps.__getitem__)
 
-    def _serve_codec(self, reports, B, first, every, fmt, voice=None, ref_of=None):
+    def _serve_codec(self, reports, B, first, every, fmt, voice=None, ref_of=None, step_of=None):
         """The codec half of serve_stream() and serve_live(): consumes the talker's (session, report) items
         (TalkerEngine.serve_iter / serve_live_iter) and yields (request, pcm, last).  A row without new frames in a
         report -- idle, or held -- rides along.  An item (None, [requests]) names requests that end without audio.
         voice (a VoiceCache) selects the route that also serves requests with reference codes, ref_of(request) ->
-        its reference codes or None (_serve_codec_voice)."""
+        its reference codes or None (_serve_codec_voice).  step_of(request) -> its speed step, asked once
+        when the request takes its slot; the tempo stage is built when the first request with another rate than 1.0
+        arrives (_slot_output), so a call without one runs the default path."""
         if voice is not None:
-            yield from self._serve_codec_voice(reports, B, first, every, fmt, voice, ref_of)
+            yield from self._serve_codec_voice(reports, B, first, every, fmt, voice, ref_of, step_of)
             return
         dec = self.speech_tokenizer.model
         up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
@@ -684,8 +702,7 @@ class TTSModel:
                     i, lo, f, ended[b], nzb = r
                     if req[b] != i:
                         req[b], discard[b], cum[b], nz[b] = i, 0, 0, 0
-                        if out is not None:
-                            out.reset(b)
+                        out = self._slot_output(out, b, 100 if step_of is None else step_of(i), fmt, B)
                     nz[b] += nzb
                     # a frame that opens a reference chunk begins the row, after chunk 0 on the 25 context frames
                     todo[b], mk = joint_walk(0, lo, f, RC, RX)
@@ -730,7 +747,7 @@ class TTSModel:
             rs.close()
             reports.close()
 
-    def _serve_codec_voice(self, reports, B, first, every, fmt, voice, ref_of):
+    def _serve_codec_voice(self, reports, B, first, every, fmt, voice, ref_of, step_of=None):
         """_serve_codec for calls with a VoiceCache: requests with reference codes are served beside the
         others.  Request i decodes cat(ref_i, codes_i): its generated frame t sits at joint position R_i + t, and the
         chunk walk (voice.joint_walk), the restarts and the 1920 x #nonzero-cb0 length rule run over joint positions.
@@ -774,8 +791,7 @@ class TTSModel:
                     i, lo, f, ended[b], nzb = r
                     if req[b] != i:
                         req[b], discard[b], extra[b], cum[b], nz[b], Rb[b], held[b] = i, 0, 0, 0, 0, 0, None
-                        if out is not None:
-                            out.reset(b)
+                        out = self._slot_output(out, b, 100 if step_of is None else step_of(i), fmt, B)
                         ref = None if ref_of is None else ref_of(i)
                         if ref is not None and len(ref) > 0:
                             e = held[b] = voice.get(dec, ref)
@@ -865,13 +881,14 @@ class TTSModel:
         the K/V capacity per row in prompt positions.  seed: the call's seed, for requests that name none; request i
         draws Philox stream i.  sample_rate / pcm_format / prefix_cache / voice_cache: as in serve_stream() -- with a
         voice_cache, a request submitted with reference codes (and its reference text: submit(..., ref_ids=...)) is
-        served; without one it stays a rejection."""
+        served; without one it stays a rejection.  A request's speaking rate is submit(speed=...)'s."""
         from .live import RequestQueue
         if not isinstance(queue, RequestQueue):
             raise ValueError(f"queue must be a qwen_tts.RequestQueue, got {type(queue).__name__}")
         fmt = self._output_format(sample_rate, pcm_format)
         voice = self._voice_bind(voice_cache)
         live_refs = {}  # request -> its reference codes, from admission until the codec half has taken them
+        live_steps = {}  # request -> its speed step when it is not 100 (submit(speed=...)), likewise
         self._prefix_bind(prefix_cache)
         B = int(max_batch)
         if not 1 <= B <= 64:
@@ -917,18 +934,40 @@ class TTSModel:
                 # (a malformed reference rejects the request here, not in the loop)
                 check_codes(self.speech_tokenizer.model, VoiceCache.codes_array(refs[0]))
                 live_refs[r.id] = refs[0]
+            if r.speed_step != 100:
+                live_steps[r.id] = r.speed_step
             return emb[0], trail[0], rgp, plan
 
         yield from self._serve_codec(
             self.engine.serve_live_iter(queue, pad, gp, prepare, slots=B, max_prompt=max_prompt, use_graph=use_graph,
                                         every=every, first=first, text_eos=cfg["tts_eos_token_id"]), B, first, every,
-            fmt, voice, lambda i: live_refs.pop(i, None))
+            fmt, voice, lambda i: live_refs.pop(i, None), lambda i: live_steps.pop(i, 100))
 
     def _output_format(self, sample_rate, pcm_format):
         """The streams' output format, validated before anything is allocated: None = the codec's own (24 kHz fp32,
         no resampler), else (resample.Plan, pcm_format)."""
         tok = self.speech_tokenizer
         return output_format(sample_rate, pcm_format, 24000 if tok is None else tok.get_output_sample_rate())
+
+    def _output_stage(self, B, fmt, steps):
+        """The output stage of a stream of B rows: None for the default output, the resampler for another format, and
+        with speed steps the tempo stage in front of it (tempo.PcmOutput)."""
+        if steps is not None:
+            return PcmOutput(B, steps, fmt, self.device)
+        return None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, self.device)
+
+    def _slot_output(self, out, b, step, fmt, B):
+        """Slot b of a serving route's output stage `out` takes a new request at speed step `step`: its state is
+        reset.  The first request at another rate than 1.0 puts the tempo stage in front of what there was (the
+        resampler keeps its state; rows at 1.0 are copied, so requests under way are not disturbed).  Returns the
+        stage."""
+        if step != 100 and not isinstance(out, PcmOutput):
+            out = PcmOutput(B, None, fmt, self.device, rs=out)
+        if isinstance(out, PcmOutput):
+            out.reset(b, step)
+        elif out is not None:
+            out.reset(b)
+        return out
 
     @staticmethod
     def _resampled(out, pcm, pend, names=None):
@@ -984,7 +1023,7 @@ class TTSModel:
         return pre, side, cs, fed
 
     def _stream_stateful(self, dec, emb, mask, trail, pad, gp, B, eos, first_chunk_frames, chunk_frames, use_graph,
-                         prefix=None, started=None, gate=None, fmt=None, plan=None):
+                         prefix=None, started=None, gate=None, fmt=None, plan=None, steps=None):
         """stream() on the incremental codec: every final frame is fed once to the decoder of its reference chunk
         and every sample computable from the frames fed so far is emitted -- 1920 n - 555 samples of a chunk after
         its n frames, i.e. no lookahead frame is waited for (the 555 samples that need it follow with the next
@@ -1016,7 +1055,7 @@ class TTSModel:
         scanned = 0                       # cb0 columns already searched for EOS
         k, cs, fed, emit_s, ctx_s = 0, None, 0, 0, 0   # reference chunk, its decoder, positions fed, samples emitted
         main, side = torch.cuda.current_stream(dev), None
-        out = None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, dev)
+        out = self._output_stage(B, fmt, steps)
         if started is not None:  # stream() began decoding the reference frames before the prompt assembly
             _, side, cs, fed = started
         elif min(R) > 0:

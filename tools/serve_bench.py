@@ -23,11 +23,12 @@ same process, alternating within every repetition, one line each; --only-stream 
 every request its own).  --prefix-cache runs the stream schedule with and without a qwen_tts.PrefixCache in
 the same process, alternating within every repetition, one line each; the cache lives for the whole process, so the
 measured runs are warm (their hits and misses are in the line).  --streaming-text puts only the first text token into
-the prefill (non_streaming_mode=False) instead of the wrapper's default.
+the prefill (non_streaming_mode=False) instead of the wrapper's default.  --speed 1.25 runs the stream
+schedule with and without that speaking rate in the same process, alternating within every repetition, one line each.
 
     python tools/serve_bench.py [--requests 8] [--slots 8] [--extra-slots 16,32] [--stream]
         [--sample-rate 16000 --pcm s16] [--ab 16000:s16,48000:f32] [--only-stream]
-        [--voices 8] [--prefix-cache] [--streaming-text]
+        [--voices 8] [--prefix-cache] [--streaming-text] [--speed 1.25]
 """
 from __future__ import annotations
 
@@ -81,6 +82,7 @@ def main():
     ap.add_argument("--voices", type=int, default=0, help="draw the instructions from this many distinct ones")
     ap.add_argument("--prefix-cache", action="store_true", help="stream schedule with and without a PrefixCache")
     ap.add_argument("--streaming-text", action="store_true", help="non_streaming_mode=False (default True)")
+    ap.add_argument("--speed", type=float, default=None, help="stream schedule with and without this speaking rate")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from qwen_tts import PrefixCache, Qwen3TTSModel
@@ -129,16 +131,19 @@ def main():
 
     formats = [(a.sample_rate, a.pcm)] + [(int(x.split(":")[0]), x.split(":")[1]) for x in a.ab.split(",") if x]
 
-    # (format, with the prefix cache) of every stream run
-    variants = [(fmt, c) for fmt in formats for c in ((False, True) if a.prefix_cache else (False,))]
+    # (format, with the prefix cache, speaking rate) of every stream run
+    variants = [(fmt, c, sp) for fmt in formats for c in ((False, True) if a.prefix_cache else (False,))
+                for sp in ((None, a.speed) if a.speed is not None else (None,))]
 
     def stream(slots, seed, var=variants[0]):
         """serve_stream: returns the samples received per request; first-chunk latencies go to first_ms"""
-        fmt, cached = var
+        fmt, cached, speed = var
         got, lat = [0] * len(reqs), {}
         out = {} if fmt == (None, "f32") else dict(sample_rate=fmt[0], pcm_format=fmt[1])
         if cached:
             out["prefix_cache"] = cache
+        if speed is not None:
+            out["speed"] = speed
         it = m.serve_stream(input_ids=[r[0] for r in reqs], instruct_ids=[r[1] for r in reqs],
                             languages=["english"] * len(reqs), non_streaming_mode=nsm, max_new_tokens=max(F) + 1,
                             seed=seed, frame_caps=F, max_batch=slots, first_chunk_frames=1,
@@ -173,7 +178,9 @@ def main():
                 # every frame's 1920 samples but each reference chunk's last 555 (fewer only where a cb0 is 0), at
                 # the output rate
                 rate = 24000 if fmt[0] is None else fmt[0]
-                assert all(0 < g <= -(-(1920 * f - 555 * -(-f // 300)) * rate // 24000) for g, f in zip(got, F)), got
+                S = 100 if var[2] is None else int(round(100 * var[2]))
+                assert all(0 < g <= -(-(-(-100 * (1920 * f - 555 * -(-f // 300)) // S)) * rate // 24000)
+                           for g, f in zip(got, F)), got
         return res
 
     def run(fn, slots):
@@ -206,9 +213,11 @@ def main():
                                           "F U[64,320], sampling, ignore_eos + per-request cap, + codec decode"}),
                   flush=True)
     if a.stream:
-        for slots, ((fmt, cached), (ts, lats, hm)) in ((s, kv) for s in slot_list for kv in run_stream(s).items()):
+        for slots, ((fmt, cached, speed), (ts, lats, hm)) in ((s, kv) for s in slot_list for kv in run_stream(s).items()):
             dt = float(np.median(ts))
             pc = {} if not a.prefix_cache else {"prefix_cache": cached}
+            if a.speed is not None:
+                pc["speed"] = 1.0 if speed is None else speed
             if cached:
                 pc.update(hits=hm[0], misses=hm[1], cache=cache.stats)
             st = getattr(eng, "serve_stats", {})
