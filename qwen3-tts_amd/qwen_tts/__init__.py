@@ -13,9 +13,10 @@ from .feed import TextFeed, TextFeedTimeout  # noqa: E402,F401
 from .live import RequestQueue  # noqa: E402,F401
 from .resample import PcmResampler  # noqa: E402,F401
 from .tempo import PcmTempo  # noqa: E402,F401
+from .prosody import PcmProsody  # noqa: E402,F401
 from .prefix import PrefixCache  # noqa: E402,F401
 from .voice import VoiceCache  # noqa: E402,F401
 
 __all__ = ["__version__", "Qwen3TTSModel", "Qwen3TTSTokenizer", "VoiceClonePromptItem", "load_voice_clone_prompt",
            "save_voice_clone_prompt", "TextFeed", "TextFeedTimeout", "RequestQueue", "PcmResampler",
-           "PcmTempo", "PrefixCache", "VoiceCache"]
+           "PcmTempo", "PcmProsody", "PrefixCache", "VoiceCache"]

@@ -154,6 +154,21 @@ class TempoArgs(ctypes.Structure):
     _fields_ = [("B", c_int), ("reserved", c_int), ("window", c_void_p), ("rows", ctypes.POINTER(TempoRow))]
 
 
+PROSODY_HIST = 1152  # QT_PROSODY_HIST
+
+
+class ProsodyRow(ctypes.Structure):
+    """qt_prosody_row: one row of a qt_prosody call (host table)"""
+    _fields_ = [("src", c_void_p), ("out", c_void_p), ("state_in", c_void_p), ("state_out", c_void_p),
+                ("table", c_void_p), ("pos", c_ll), ("m0", c_ll), ("pos0", c_ll), ("cap", c_ll), ("n", c_int),
+                ("count", c_int), ("up", c_int), ("down", c_int), ("half", c_int), ("taps", c_int), ("gain", c_float),
+                ("limited", c_int), ("flush", c_int), ("reserved", c_int)]
+
+
+class ProsodyArgs(ctypes.Structure):
+    _fields_ = [("B", c_int), ("reserved", c_int), ("rows", ctypes.POINTER(ProsodyRow))]
+
+
 KV_ADOPT, KV_EXPORT = 0, 1  # QT_KV_*
 
 
@@ -202,7 +217,7 @@ EXPORTS = ["qt_gemm", "qt_gemm_route", "qt_tile_weight", "qt_qkv_post", "qt_atte
            "qt_stream_window", "qt_stream_rows", "qt_trail_append", "qt_kv_prefix",
            "qt_row_state", "qt_row_state_row_bytes",
            "qt_codec_row_state", "qt_codec_row_state_bytes", "qt_codec_feed_codes",
-           "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample", "qt_tempo",
+           "qt_rvq_gather", "qt_snake", "qt_dwconv_ln", "qt_clamp_pcm", "qt_resample", "qt_tempo", "qt_prosody",
            "qt_pad_time", "qt_zero_tail", "qt_layernorm", "qt_rvq_encode", "qt_rvq_encode_ws_bytes", "qt_mel_logmag", "qt_time_stats",
            "qt_scale_add", "qt_bcast_rows", "qt_build_id"]
 
@@ -265,6 +280,7 @@ def load_library(path: str = LIB_PATH):
         "qt_clamp_pcm": [P, c_int, c_ll, P, P],
         "qt_resample": [P, P],
         "qt_tempo": [P, P],
+        "qt_prosody": [P, P],
         "qt_decode_attn_ws_bytes": [c_int, c_int, c_int, c_int, c_int],
         "qt_decode_attn_oproj": [P, P],
         "qt_attn_oproj_ws_bytes": [c_int, c_int],

@@ -20,7 +20,7 @@ import torch
 from .. import audio as _audio
 from .. import kernels as _kernels
 from .. import resample as _resample
-from .. import tempo as _tempo
+from .. import prosody as _prosody
 from ..live import SAMPLING_DEFAULTS, RequestQueue
 from ..model import TTSModel
 from ..text import load_processor
@@ -295,13 +295,16 @@ class Qwen3TTSModel:
     @torch.no_grad()
     def generate_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False,
                              voice_clone_prompt=None, non_streaming_mode=False, sample_rate=None, pcm_format="f32",
-                             speed=None, **kwargs):
+                             speed=None, pitch=None, volume_gain_db=None, **kwargs):
         """speed (not in the reference): the speaking rate, 0.5 to 2.0, a number or one per text -- the
-        wavs time-stretched on the device (after the reference's cut, before the resampler and the host copy)."""
+        wavs time-stretched on the device (after the reference's cut, before the resampler and the host copy).
+        pitch / volume_gain_db (not in the reference): the pitch in semitones, -12 to 12 (resampling
+        pitch: formants move with it), and the gain in dB, -96 to 16 (a positive gain is peak-limited at 1.0), a
+        number or one per text, applied on the device between the time-stretch and the resampler."""
         self._output_format(sample_rate, pcm_format)
         input_ids, ref_ids, vcp, languages = self._voice_clone_inputs(text, language, ref_audio, ref_text,
                                                                       x_vector_only_mode, voice_clone_prompt)
-        steps = None if speed is None else _tempo.speed_steps(speed, len(input_ids))
+        steps = _prosody.request_steps(speed, pitch, volume_gain_db, len(input_ids))
         codes, _ = self.model.generate(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp, languages=languages,
                                        non_streaming_mode=non_streaming_mode,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
@@ -328,15 +331,15 @@ class Qwen3TTSModel:
     def stream_voice_clone(self, text, language=None, ref_audio=None, ref_text=None, x_vector_only_mode=False,
                            voice_clone_prompt=None, non_streaming_mode=False, first_chunk_frames=1, chunk_frames=48,
                            sample_rate=None, pcm_format="f32", max_batch=None, voice_cache=None, speed=None,
-                           **kwargs):
+                           pitch=None, volume_gain_db=None, **kwargs):
         """New surface (no reference counterpart, SURVEY.md §8f-1 + 8f-2): streaming voice clone.  Same inputs as
         generate_voice_clone (reference audio is encoded / x-vectored at submit); yields (utterance index, pcm chunk
         np.float32, sample rate, is_last).  Per utterance the chunks concatenate to generate_voice_clone()'s PCM: in
         ICL mode the reference codes are decoded in front of the generated ones and the output starts at their
         boundary -- the wrapper's proportional cut keeps floor(555 R / T) more samples of the reference's tail, a
         length-dependent point a stream cannot know in advance (TTSModel._stream_stateful).  sample_rate /
-        pcm_format / speed: as in stream().  max_batch: with more texts than max_batch, stream them by continuous batching
-        through max_batch rows (TTSModel.serve_stream); ICL prompts then need voice_cache, a qwen_tts.VoiceCache that
+        pcm_format / speed / pitch / volume_gain_db: as in stream().  max_batch: with more texts than max_batch, stream
+        them by continuous batching through max_batch rows (TTSModel.serve_stream); ICL prompts then need voice_cache, a qwen_tts.VoiceCache that
         keeps each voice's codec state across requests (VoiceCache.warm fills it ahead of the first request)."""
         sr = self._output_format(sample_rate, pcm_format)
         input_ids, ref_ids, vcp, languages = self._voice_clone_inputs(text, language, ref_audio, ref_text,
@@ -345,7 +348,8 @@ class Qwen3TTSModel:
                                               languages=languages, non_streaming_mode=non_streaming_mode,
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
                                               sample_rate=sample_rate, pcm_format=pcm_format, max_batch=max_batch,
-                                              voice_cache=voice_cache, speed=speed,
+                                              voice_cache=voice_cache, speed=speed, pitch=pitch,
+                                              volume_gain_db=volume_gain_db,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, (pcm if pcm.dtype == torch.int16 else pcm.to(torch.float32)).cpu().numpy(), sr, last
 
@@ -390,9 +394,10 @@ class Qwen3TTSModel:
     # ---------------------------------------------------------------- voice design (W:637-728)
     @torch.no_grad()
     def generate_voice_design(self, text, instruct, language=None, non_streaming_mode=True, sample_rate=None,
-                              pcm_format="f32", prefix_cache=None, speed=None, **kwargs):
+                              pcm_format="f32", prefix_cache=None, speed=None, pitch=None, volume_gain_db=None,
+                              **kwargs):
         """prefix_cache (not in the reference): a qwen_tts.PrefixCache that keeps each instruction's talker K/V across
-        calls (TTSModel.generate).  speed: as in generate_voice_clone."""
+        calls (TTSModel.generate).  speed / pitch / volume_gain_db: as in generate_voice_clone."""
         self._output_format(sample_rate, pcm_format)
         if self.model.tts_model_type != "voice_design":
             raise ValueError(f"model with tts_model_type: {self.model.tts_model_type} does not support "
@@ -411,7 +416,7 @@ class Qwen3TTSModel:
         self._validate_languages(languages)
         input_ids = self._tokenize_texts([self._build_assistant_text(t) for t in texts])
         ins_ids = [None if not x else self._tokenize_texts([self._build_instruct_text(x)])[0] for x in instructs]
-        steps = None if speed is None else _tempo.speed_steps(speed, len(input_ids))
+        steps = _prosody.request_steps(speed, pitch, volume_gain_db, len(input_ids))
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        non_streaming_mode=non_streaming_mode, prefix_cache=prefix_cache,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
@@ -447,12 +452,14 @@ class Qwen3TTSModel:
 
     @torch.no_grad()
     def generate_custom_voice(self, text, speaker, language=None, instruct=None, non_streaming_mode=True,
-                              sample_rate=None, pcm_format="f32", prefix_cache=None, speed=None, **kwargs):
+                              sample_rate=None, pcm_format="f32", prefix_cache=None, speed=None, pitch=None,
+                              volume_gain_db=None, **kwargs):
         """prefix_cache (not in the reference): as in generate_voice_design; the 0.6B models drop the instruction
-        (W:799), so their requests leave the cache untouched.  speed: as in generate_voice_clone."""
+        (W:799), so their requests leave the cache untouched.  speed / pitch / volume_gain_db: as in
+        generate_voice_clone."""
         self._output_format(sample_rate, pcm_format)
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
-        steps = None if speed is None else _tempo.speed_steps(speed, len(input_ids))
+        steps = _prosody.request_steps(speed, pitch, volume_gain_db, len(input_ids))
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        speakers=speakers, non_streaming_mode=non_streaming_mode,
                                        prefix_cache=prefix_cache,
@@ -462,7 +469,8 @@ class Qwen3TTSModel:
     @torch.no_grad()
     def stream(self, text, speaker=None, language=None, instruct=None, non_streaming_mode=None,
                first_chunk_frames=1, chunk_frames=48, left_context=None, max_batch=None, text_feed=None,
-               sample_rate=None, pcm_format="f32", prefix_cache=None, speed=None, **kwargs):
+               sample_rate=None, pcm_format="f32", prefix_cache=None, speed=None, pitch=None, volume_gain_db=None,
+               **kwargs):
         """New surface (no reference counterpart): streaming custom-voice generation.
         Yields (utterance index, pcm chunk np.float32, sample rate, is_last) while the batch decodes: the first
         chunk arrives after prefill + `first_chunk_frames` decode frames (1 frame: 1365 samples = 57 ms of audio,
@@ -492,6 +500,11 @@ class Qwen3TTSModel:
         on the device by a stateful stage (qwen_tts.tempo.PcmTempo) in front of the resampler: per utterance they
         concatenate to the stretched whole, ceil(N / speed) samples, whatever the chunking.
 
+        pitch / volume_gain_db: the pitch in semitones, -12 to 12, and the gain in dB, -96 to 16, a number
+        or one per utterance, applied by a stateful device stage (qwen_tts.prosody.PcmProsody) between the two.  Pitch
+        is resampling pitch (formants move with it; the duration stays that of `speed`, and speed divided by the pitch
+        ratio must lie in [0.5, 2.0]); a positive gain is peak-limited, so no sample leaves above 1.0.
+
         prefix_cache: a qwen_tts.PrefixCache -- an utterance whose instruction is cached skips that part of its
         prefill (TTSModel.generate)."""
         sr = self._output_format(sample_rate, pcm_format)
@@ -506,7 +519,8 @@ class Qwen3TTSModel:
                                               first_chunk_frames=first_chunk_frames, chunk_frames=chunk_frames,
                                               left_context=left_context, max_batch=max_batch, text_feed=text_feed,
                                               sample_rate=sample_rate, pcm_format=pcm_format,
-                                              prefix_cache=prefix_cache, speed=speed,
+                                              prefix_cache=prefix_cache, speed=speed, pitch=pitch,
+                                              volume_gain_db=volume_gain_db,
                                               **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs)):
             yield i, (pcm if pcm.dtype == torch.int16 else pcm.to(torch.float32)).cpu().numpy(), sr, last
 
@@ -520,7 +534,8 @@ class Qwen3TTSModel:
 
     def request_queue(self, timeout: float = 30.0):
         """A qwen_tts.RequestQueue for serve_live() that also takes strings:
-        submit(text=..., instruct=..., language=..., speaker=..., open_text=False, speed=None, **sampling) tokenizes as stream()
+        submit(text=..., instruct=..., language=..., speaker=..., open_text=False, speed=None, pitch=None,
+        volume_gain_db=None, **sampling) tokenizes as stream()
         does (with open_text, `text` is the first piece and the rest follows through push_text / close_text), and
         fills the sampling parameters a request leaves out from generation_config.json.  non_streaming_mode defaults
         to True as in generate_custom_voice(), and to False with open_text."""

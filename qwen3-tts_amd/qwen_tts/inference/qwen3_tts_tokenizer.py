@@ -18,6 +18,7 @@ from torch.nn.utils.rnn import pad_sequence
 
 from .. import audio as _audio
 from .. import resample as _resample
+from .. import prosody as _prosody
 from .. import tempo as _tempo
 from ..codec import CodecDecoder
 from ..encoder import TokenizerEncoder, encoder_specs
@@ -98,8 +99,9 @@ class Qwen3TTSTokenizer:
         """Z:259-365.  sample_rate / pcm_format (the reference has neither): the wavs resampled on the
         device before the host copy (qwen_tts.PcmResampler.one_shot), float32 or int16, and the requested rate.
         _cut (generate_voice_clone): per wav None or (R, T), dropping its first int(R / T * len) samples before the
-        resampler sees it.  _steps (the generate_* wrappers' speed): per wav its speed step, applied after
-        the cut and before the resampler (qwen_tts.tempo.PcmTempo.one_shot)."""
+        resampler sees it.  _steps (the generate_* wrappers' speed, pitch and gain): per wav its
+        entry of prosody.request_steps(), applied after the cut and before the resampler (PcmTempo.one_shot, then
+        PcmProsody.one_shot)."""
         fmt = _resample.output_format(sample_rate, pcm_format, self.get_output_sample_rate())
         if hasattr(encoded, "audio_codes"):
             codes_list = encoded.audio_codes
@@ -124,9 +126,19 @@ class Qwen3TTSTokenizer:
                 if _cut is not None:
                     wavs = [w if c is None else w[int(c[0] / max(c[1], 1) * w.shape[0]):] for w, c in zip(wavs, _cut)]
                 if _steps is not None:
-                    tp = _tempo.PcmTempo(1, self.device)
-                    wavs = [w.to(torch.float32) if s == 100 else tp.one_shot(w.to(torch.float32), s)
-                            for w, s in zip(wavs, _steps)]
+                    tp, pp = _tempo.PcmTempo(1, self.device), None
+                    done = []
+                    for w, step in zip(wavs, _steps):
+                        S, pro = _prosody.split_step(step)
+                        T, db = (S, 0.0) if pro is None else pro
+                        n, w = int(w.shape[0]), w.to(torch.float32)
+                        if T != 100:
+                            w = tp.one_shot(w, T)
+                        if pro is not None:
+                            pp = pp or _prosody.PcmProsody(1, self.device)
+                            w = pp.one_shot(w, T, S, db, cap=_tempo.out_len(n, S))
+                        done.append(w)
+                    wavs = done
                 if fmt is None:
                     return [w.cpu().numpy() for w in wavs], self.get_output_sample_rate()
                 x = pad_sequence([w.to(torch.float32) for w in wavs], batch_first=True)

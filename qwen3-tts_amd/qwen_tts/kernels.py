@@ -697,6 +697,20 @@ def tempo(window, rows):
     check(_hip.lib().qt_tempo(ctypes.byref(a), stream()), "qt_tempo")
 
 
+def prosody(rows):
+    """qt_prosody: rows = one (src, out, state_in, state_out, table, pos, m0, pos0, cap, n, count, up, down, half,
+    taps, gain, limited, flush) per row, pointers as ints or None (prosody.PcmProsody.push builds them and owns the
+    counters)."""
+    tab = (_hip.ProsodyRow * len(rows))()
+    for r, (src, out, sin, sout, table, pos, m0, pos0, cap, n, count, up, down, half, taps, gain, limited,
+            flush) in zip(tab, rows):
+        r.src, r.out, r.state_in, r.state_out, r.table = src, out, sin, sout, table
+        r.pos, r.m0, r.pos0, r.cap, r.n, r.count = pos, m0, pos0, cap, n, count
+        r.up, r.down, r.half, r.taps, r.gain, r.limited, r.flush = up, down, half, taps, gain, limited, flush
+    a = _hip.ProsodyArgs(len(rows), 0, tab)
+    check(_hip.lib().qt_prosody(ctypes.byref(a), stream()), "qt_prosody")
+
+
 def rope_tables(head_dim: int, theta: float, npos: int, device):
     """cos/sin [npos][D/2] computed exactly as the reference (fp32 on CPU, M:526-592), then uploaded."""
     inv = 1.0 / (theta ** (torch.arange(0, head_dim, 2, dtype=torch.int64).to(dtype=torch.float) / head_dim))

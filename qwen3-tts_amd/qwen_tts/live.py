@@ -40,6 +40,7 @@ class LiveRequest:
     sampling: dict = field(default_factory=dict)
     ref_ids: Optional[List[int]] = None  # a voice-clone (ICL) request's reference text (serve_live(voice_cache=...))
     speed_step: int = 100  # the request's speaking rate in hundredths (tempo.speed_steps)
+    prosody: Optional[tuple] = None  # (T, db) of a request with a pitch or a gain (prosody.steps), else None
 
 
 class RequestQueue:
@@ -78,15 +79,16 @@ class RequestQueue:
     # ------------------------------------------------------------------ producers (any thread)
     def submit(self, input_ids, *, instruct_ids=None, language=None, speaker=None, voice_clone_prompt=None,
                non_streaming_mode=False, open_text=False, frame_cap=None, ref_ids=None, speed=None,
-               **sampling) -> int:
+               pitch=None, volume_gain_db=None, **sampling) -> int:
         """Queue a request; returns its id.  **sampling: the per-request sampling parameters of generate() (do_sample,
         top_k, top_p, temperature, the four subtalker_* values, repetition_penalty, seed).  What the loop finds
         unservable when it assembles the prompt (prompt too long, unknown speaker, ...) ends up in `rejected`.
         ref_ids: the reference text's ids of a voice-clone request in ICL mode (its voice_clone_prompt carries
         reference codes), as generate() takes them; the loop serves such a request when it was given a voice_cache.
-        speed: the request's speaking rate, 0.5 to 2.0."""
-        from .tempo import speed_steps
-        step = (speed_steps(speed, 1) or [100])[0]
+        speed: the request's speaking rate, 0.5 to 2.0.  pitch / volume_gain_db: its pitch in semitones,
+        -12 to 12, and its gain in dB, -96 to 16."""
+        from .prosody import request_steps, split_step
+        step, pro = split_step((request_steps(speed, pitch, volume_gain_db, 1) or [100])[0])
         unknown = set(sampling) - set(SAMPLING_DEFAULTS)
         if unknown:
             raise TypeError(f"submit() got unexpected keyword arguments {sorted(unknown)}")
@@ -102,7 +104,7 @@ class RequestQueue:
             self._next += 1
             self._new.append(LiveRequest(i, ids, ins, language, speaker, voice_clone_prompt, bool(non_streaming_mode),
                                          bool(open_text), None if frame_cap is None else int(frame_cap),
-                                         {**SAMPLING_DEFAULTS, **sampling}, ref, step))
+                                         {**SAMPLING_DEFAULTS, **sampling}, ref, step, pro))
             self._live.add(i)
             if open_text:
                 self._open[i] = True

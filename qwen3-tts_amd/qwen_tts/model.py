@@ -13,7 +13,8 @@ import torch
 from . import kernels as K
 from .prefix import PrefixCache, PrefixPlan
 from .resample import PcmResampler, output_format
-from .tempo import PcmOutput, speed_steps
+from .prosody import request_steps, split_step
+from .tempo import PcmOutput
 from .talker import MIN_NEW_TOKENS, GenParams, HandoffWatch, TalkerEngine
 from .voice import VoiceCache, boundary_skip, check_codes, joint_walk, plan_feed
 
@@ -405,7 +406,7 @@ class TTSModel:
                subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False, seed=None,
                first_chunk_frames=1, chunk_frames=48, left_context=None, use_graph=True, max_batch=None,
                text_feed=None, sample_rate=None, pcm_format="f32", prefix_cache=None, voice_cache=None, speed=None,
-               **kwargs):
+               pitch=None, volume_gain_db=None, **kwargs):
         """Streaming generation (the reference has none): yields (row, pcm, last) as frames finish.
 
         Per row the chunks concatenate to the one-shot generate() + decode() PCM (Z:259-365): the reference
@@ -450,16 +451,26 @@ class TTSModel:
         default's, ceil(100 N / S) samples, bit for bit whatever the chunking.  The output for the last 25 to 35 ms
         of input is held back for the search and follows with the next chunk; last=True flushes.  A request at 1.0
         keeps the default's bits; with every request at 1.0 (or None) no stage is built.  The stateless left_context
-        form does not serve it."""
+        form does not serve it.
+
+        pitch / volume_gain_db: the pitch in semitones, -12 to 12, and the gain in dB, -96 to 16 -- each a
+        number, or one per request.  Pitch is resampling pitch (formants move with it): the tempo stage runs the
+        request at T = floor(S / 2^(pitch/12) + 0.5) and prosody.PcmProsody resamples its output by T/S, so the
+        duration stays ceil(100 N / S) samples and the realised pitch ratio is S/T (within 17.4 cents of the request).
+        A positive gain runs a look-ahead peak limiter: no sample leaves above 1.0, and 127 more samples (under 6 ms)
+        are held back.  The chunks concatenate to the one-shot chain of the default's samples bit for bit; a request
+        at 0 / 0 keeps the default's bits, and with every request there nothing is built.  speed divided by the pitch
+        ratio must lie in [0.5, 2.0].  The stateless left_context form does not serve them."""
         fmt = self._output_format(sample_rate, pcm_format)
-        steps = None if speed is None else speed_steps(speed, 0 if input_ids is None else len(input_ids))
+        steps = request_steps(speed, pitch, volume_gain_db, 0 if input_ids is None else len(input_ids))
         self._voice_bind(voice_cache)
         lens = self._prefix_bind(prefix_cache)
         if fmt is not None and left_context is not None:
             raise NotImplementedError("stream(left_context=...) with sample_rate / pcm_format: use the default "
                                       "stateful stream")
         if steps is not None and left_context is not None:
-            raise NotImplementedError("stream(left_context=...) with speed: use the default stateful stream")
+            raise NotImplementedError("stream(left_context=...) with speed, pitch or volume_gain_db: use the default "
+                                      "stateful stream")
         if text_feed is not None:
             yield from self._stream_fed(text_feed, input_ids, instruct_ids, voice_clone_prompt, languages, speakers,
                                         non_streaming_mode, left_context, max_batch, first_chunk_frames, chunk_frames,
@@ -478,7 +489,8 @@ class TTSModel:
                 subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed,
                 max_batch=max_batch, first_chunk_frames=first_chunk_frames,
                 chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, sample_rate=sample_rate,
-                pcm_format=pcm_format, prefix_cache=prefix_cache, voice_cache=voice_cache, speed=speed, **kwargs)
+                pcm_format=pcm_format, prefix_cache=prefix_cache, voice_cache=voice_cache, speed=speed,
+                pitch=pitch, volume_gain_db=volume_gain_db, **kwargs)
             return
         dec = self.speech_tokenizer.model
         up = dec.total_upsample
@@ -615,7 +627,7 @@ class TTSModel:
                      subtalker_temperature=0.9, eos_token_id=None, repetition_penalty=1.05, ignore_eos=False,
                      seed=None, max_batch=8, first_chunk_frames=1, chunk_frames=8, use_graph=True, philox_ids=None,
                      frame_caps=None, sample_rate=None, pcm_format="f32", prefix_cache=None, voice_cache=None,
-                     speed=None, **kwargs):
+                     speed=None, pitch=None, volume_gain_db=None, **kwargs):
         """Streaming from the continuously batched route (the reference has neither): the requests are
         decoded through max_batch batch rows as generate(max_batch=...) decodes them, and each request's audio
         leaves as it is generated -- yields (request index, pcm, last).
@@ -632,7 +644,7 @@ class TTSModel:
         sample_rate / pcm_format: as in stream() -- one resampler launch per codec feed for all slots, a slot's state
         reset when its request changes.  prefix_cache: as in generate() -- the first prefill and every refill use it.
         speed: as in stream(), a number or one per request -- a slot's tempo state is reset, and takes the new
-        request's rate, when its request changes.
+        request's rate, when its request changes.  pitch / volume_gain_db: as in stream(), likewise.
 
         voice_cache: a qwen_tts.VoiceCache.  With one, prompts whose ref_code[i] is not None (ICL) are
         served too, mixed freely with x-vector-only and plain requests: request i's audio is the decode of
@@ -641,7 +653,7 @@ class TTSModel:
         codec state behind the voice's reference frames from the cache (built on a miss on a one-row stream of its
         own), so a request's first chunk is 1920 x first_chunk_frames - 555 samples as for any other request."""
         fmt = self._output_format(sample_rate, pcm_format)
-        steps = None if speed is None else speed_steps(speed, 0 if input_ids is None else len(input_ids))
+        steps = request_steps(speed, pitch, volume_gain_db, 0 if input_ids is None else len(input_ids))
         voice = self._voice_bind(voice_cache)
         refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
         if voice is None and refs is not None and any(r is not None for r in refs):
@@ -881,7 +893,8 @@ class TTSModel:
         the K/V capacity per row in prompt positions.  seed: the call's seed, for requests that name none; request i
         draws Philox stream i.  sample_rate / pcm_format / prefix_cache / voice_cache: as in serve_stream() -- with a
         voice_cache, a request submitted with reference codes (and its reference text: submit(..., ref_ids=...)) is
-        served; without one it stays a rejection.  A request's speaking rate is submit(speed=...)'s."""
+        served; without one it stays a rejection.  A request's speaking rate, pitch and gain are submit(speed=...,
+        pitch=..., volume_gain_db=...)'s."""
         from .live import RequestQueue
         if not isinstance(queue, RequestQueue):
             raise ValueError(f"queue must be a qwen_tts.RequestQueue, got {type(queue).__name__}")
@@ -934,8 +947,8 @@ class TTSModel:
                 # (a malformed reference rejects the request here, not in the loop)
                 check_codes(self.speech_tokenizer.model, VoiceCache.codes_array(refs[0]))
                 live_refs[r.id] = refs[0]
-            if r.speed_step != 100:
-                live_steps[r.id] = r.speed_step
+            if r.speed_step != 100 or r.prosody is not None:
+                live_steps[r.id] = r.speed_step if r.prosody is None else (r.speed_step,) + tuple(r.prosody)
             return emb[0], trail[0], rgp, plan
 
         yield from self._serve_codec(
@@ -951,20 +964,24 @@ class TTSModel:
 
     def _output_stage(self, B, fmt, steps):
         """The output stage of a stream of B rows: None for the default output, the resampler for another format, and
-        with speed steps the tempo stage in front of it (tempo.PcmOutput)."""
+        with speed steps the tempo stage in front of it, and with a pitch or a gain the prosody stage behind that
+        (tempo.PcmOutput).  steps: prosody.request_steps()'s entries."""
         if steps is not None:
-            return PcmOutput(B, steps, fmt, self.device)
+            S, pro = zip(*(split_step(s) for s in steps))
+            return PcmOutput(B, S, fmt, self.device, prosody=pro if any(v is not None for v in pro) else None)
         return None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, self.device)
 
     def _slot_output(self, out, b, step, fmt, B):
-        """Slot b of a serving route's output stage `out` takes a new request at speed step `step`: its state is
-        reset.  The first request at another rate than 1.0 puts the tempo stage in front of what there was (the
-        resampler keeps its state; rows at 1.0 are copied, so requests under way are not disturbed).  Returns the
-        stage."""
-        if step != 100 and not isinstance(out, PcmOutput):
+        """Slot b of a serving route's output stage `out` takes a new request at speed step `step` (an entry of
+        prosody.request_steps(): with its tempo step and gain where it has a pitch or a gain): its state is reset.
+        The first request at another rate than 1.0, or with a pitch or a gain, puts the stages in front of what there
+        was (the resampler keeps its state; default rows are copied, so requests under way are not disturbed).
+        Returns the stage."""
+        step, pro = split_step(step)
+        if (step != 100 or pro is not None) and not isinstance(out, PcmOutput):
             out = PcmOutput(B, None, fmt, self.device, rs=out)
         if isinstance(out, PcmOutput):
-            out.reset(b, step)
+            out.reset(b, step, pro)
         elif out is not None:
             out.reset(b)
         return out

@@ -53,6 +53,13 @@ def plan(sample_rate, in_rate=IN_RATE) -> Plan:
     if q > MAX_Q:
         raise ValueError(f"sample_rate {sample_rate} from {in_rate} Hz is the ratio {up}/{down}: ratios above "
                          f"{MAX_Q} are not served (8000, 12000, 16000, 22050, 32000, 44100 and 48000 are)")
+    return Plan(sample_rate, in_rate, up, down, *filter_taps(up, down))
+
+
+def filter_taps(up: int, down: int):
+    """(half, taps, h, table) of the ratio up/down in lowest terms: the filter every stage that resamples shares
+    (the pitch stage of prosody.py builds its per-request filters here too)."""
+    q = max(up, down)
     half = 10 * q
     j = np.arange(2 * half + 1, dtype=np.float64)
     h = np.kaiser(2 * half + 1, 5.0) * np.sinc((j - half) / q)
@@ -65,7 +72,7 @@ def plan(sample_rate, in_rate=IN_RATE) -> Plan:
     table = np.ascontiguousarray(table.reshape(taps, up).T)  # ... -> [up][taps]
     h.setflags(write=False)
     table.setflags(write=False)
-    return Plan(sample_rate, in_rate, up, down, half, taps, h, table)
+    return half, taps, h, table
 
 
 def ready(p: Plan, n_total: int, flush: bool = False) -> int:

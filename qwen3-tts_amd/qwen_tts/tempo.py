@@ -3,7 +3,8 @@
 Host side, in numpy, importable without a GPU: the definition -- `a()`, `out_len()`, `need()`, `ready()` (the streaming
 emission rule), `stretch()` (the reference) and `speed_steps()` (validation of a caller's `speed`).  Device side:
 `PcmTempo`, the stateful, chunk-invariant stage of csrc/tempo.hip (qt_tempo) -- one launch per push for all rows, host
-counters only, no read-back.  It sits between the codec's PCM and the resampler (`PcmOutput` chains the two).
+counters only, no read-back.  It sits between the codec's PCM and the resampler (`PcmOutput` chains the two, with the
+pitch and volume stage of prosody.py, DESIGN §22, between them where a request asks for it).
 
 Definition: WSOLA with an integer-exact search.  x = a row's input (24 kHz fp32, n samples, zero outside [0, n)),
 S = round(100 * speed) in [50, 200], a(j) = (j * HS * S) // 100.  The output has out_len(n) = ceil(100 n / S) samples,
@@ -295,14 +296,16 @@ class PcmTempo:
 
 
 class PcmOutput:
-    """The output side of a stream with a speaking rate: PcmTempo, then (for another sample rate or format) the
-    PcmResampler, behind the interface the routes use for the resampler alone -- rows, reset(row), push(src, offsets,
-    lengths, flush).  Two launches per push for all rows; the tempo stage's counts are the host rule's, so its output
-    feeds the resampler as a 1-D source without a synchronisation."""
+    """The output side of a stream with a speaking rate, a pitch or a gain: PcmTempo, then (where a request asks for
+    a pitch or a gain) prosody.PcmProsody, then (for another sample rate or format) the PcmResampler,
+    behind the interface the routes use for the resampler alone -- rows, reset(row), push(src, offsets, lengths, flush).  At
+    most three launches per push for all rows; every stage's counts are its host rule's, so its output feeds the next
+    as a 1-D source without a synchronisation."""
 
-    def __init__(self, rows, steps, fmt, device, rs=None):
+    def __init__(self, rows, steps, fmt, device, rs=None, prosody=None):
         """fmt: resample.output_format()'s (Plan, pcm_format) or None; rs: a PcmResampler of that format to go on
-        with (its rows keep their state) instead of a new one."""
+        with (its rows keep their state) instead of a new one; prosody: per row None or (T, db), the row's tempo
+        step and gain (prosody.steps) -- the pitch stage is built with the first row that has one."""
         from .resample import PcmResampler
         self.rows = int(rows)
         self.tempo = PcmTempo(rows, device)
@@ -310,22 +313,49 @@ class PcmOutput:
             rs = PcmResampler(rows, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, device)
         self.rs = rs
         self.steps = [100] * self.rows if steps is None else [check_steps(s) for s in steps]
+        self.tsteps = list(self.steps)   # the steps the tempo stage runs at: T of prosody.py, S without a pitch
+        self.pro = None
+        for b, v in enumerate(prosody or ()):
+            self._prosody(b, v)
 
-    def reset(self, row, step=None):
+    def _prosody(self, row, v):
+        S = self.steps[row]
+        T, db = (S, 0.0) if v is None else v
+        self.tsteps[row] = check_steps(T)
+        if self.pro is None:
+            if T == S and db == 0:
+                return
+            from .prosody import PcmProsody
+            # (rows under way are copied from here on: a row at T == S and 0 dB passes what it takes)
+            self.pro = PcmProsody(self.rows, self.tempo.device)
+        self.pro.reset(row, T, S, db)
+
+    def reset(self, row, step=None, prosody=None):
         self.tempo.reset(row)
         if self.rs is not None:
             self.rs.reset(row)
         if step is not None:
             self.steps[row] = check_steps(step)
+        self._prosody(row, prosody)
 
     def push(self, src, offsets, lengths, flush):
         if isinstance(flush, bool):
             flush = [flush] * self.rows
-        outs = self.tempo.push(src, offsets, lengths, flush, self.steps)
+        outs = self.tempo.push(src, offsets, lengths, flush, self.tsteps)
+        last = self.tempo.last
+        if self.pro is not None:
+            # a request of N samples yields out_len(N, S) whatever its pitch: the cut at flush
+            caps = [out_len(self.tempo.taken[b], self.steps[b]) if flush[b] else None for b in range(self.rows)]
+            outs = self.pro.push(last, *self._spans(outs), flush, caps)
+            last = self.pro.last
         if self.rs is None:
             return outs
+        return self.rs.push(last, *self._spans(outs), flush)
+
+    @staticmethod
+    def _spans(outs):
         offs, at = [], 0
         for o in outs:
             offs.append(at)
             at += o.numel()
-        return self.rs.push(self.tempo.last, offs, [o.numel() for o in outs], flush)
+        return offs, [o.numel() for o in outs]

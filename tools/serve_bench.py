@@ -25,10 +25,12 @@ the same process, alternating within every repetition, one line each; the cache 
 measured runs are warm (their hits and misses are in the line).  --streaming-text puts only the first text token into
 the prefill (non_streaming_mode=False) instead of the wrapper's default.  --speed 1.25 runs the stream
 schedule with and without that speaking rate in the same process, alternating within every repetition, one line each.
+--pitch 3 and / or --volume-gain-db 6 do the same with that pitch and gain (together with --speed: all of
+them on against all of them off).
 
     python tools/serve_bench.py [--requests 8] [--slots 8] [--extra-slots 16,32] [--stream]
         [--sample-rate 16000 --pcm s16] [--ab 16000:s16,48000:f32] [--only-stream]
-        [--voices 8] [--prefix-cache] [--streaming-text] [--speed 1.25]
+        [--voices 8] [--prefix-cache] [--streaming-text] [--speed 1.25] [--pitch 3] [--volume-gain-db 6]
 """
 from __future__ import annotations
 
@@ -83,6 +85,8 @@ def main():
     ap.add_argument("--prefix-cache", action="store_true", help="stream schedule with and without a PrefixCache")
     ap.add_argument("--streaming-text", action="store_true", help="non_streaming_mode=False (default True)")
     ap.add_argument("--speed", type=float, default=None, help="stream schedule with and without this speaking rate")
+    ap.add_argument("--pitch", type=float, default=None, help="... and with and without this pitch in semitones")
+    ap.add_argument("--volume-gain-db", type=float, default=None, help="... and with and without this gain in dB")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from qwen_tts import PrefixCache, Qwen3TTSModel
@@ -131,9 +135,10 @@ def main():
 
     formats = [(a.sample_rate, a.pcm)] + [(int(x.split(":")[0]), x.split(":")[1]) for x in a.ab.split(",") if x]
 
-    # (format, with the prefix cache, speaking rate) of every stream run
+    # (format, with the prefix cache, (speaking rate, pitch, gain) or None) of every stream run
+    ab = a.speed is not None or a.pitch is not None or a.volume_gain_db is not None
     variants = [(fmt, c, sp) for fmt in formats for c in ((False, True) if a.prefix_cache else (False,))
-                for sp in ((None, a.speed) if a.speed is not None else (None,))]
+                for sp in ((None, (a.speed, a.pitch, a.volume_gain_db)) if ab else (None,))]
 
     def stream(slots, seed, var=variants[0]):
         """serve_stream: returns the samples received per request; first-chunk latencies go to first_ms"""
@@ -143,7 +148,7 @@ def main():
         if cached:
             out["prefix_cache"] = cache
         if speed is not None:
-            out["speed"] = speed
+            out.update({k: v for k, v in zip(("speed", "pitch", "volume_gain_db"), speed) if v is not None})
         it = m.serve_stream(input_ids=[r[0] for r in reqs], instruct_ids=[r[1] for r in reqs],
                             languages=["english"] * len(reqs), non_streaming_mode=nsm, max_new_tokens=max(F) + 1,
                             seed=seed, frame_caps=F, max_batch=slots, first_chunk_frames=1,
@@ -178,7 +183,7 @@ def main():
                 # every frame's 1920 samples but each reference chunk's last 555 (fewer only where a cb0 is 0), at
                 # the output rate
                 rate = 24000 if fmt[0] is None else fmt[0]
-                S = 100 if var[2] is None else int(round(100 * var[2]))
+                S = 100 if var[2] is None or var[2][0] is None else int(round(100 * var[2][0]))
                 assert all(0 < g <= -(-(-(-100 * (1920 * f - 555 * -(-f // 300)) // S)) * rate // 24000)
                            for g, f in zip(got, F)), got
         return res
@@ -217,7 +222,11 @@ def main():
             dt = float(np.median(ts))
             pc = {} if not a.prefix_cache else {"prefix_cache": cached}
             if a.speed is not None:
-                pc["speed"] = 1.0 if speed is None else speed
+                pc["speed"] = 1.0 if speed is None else speed[0]
+            if a.pitch is not None:
+                pc["pitch"] = 0.0 if speed is None else speed[1]
+            if a.volume_gain_db is not None:
+                pc["volume_gain_db"] = 0.0 if speed is None else speed[2]
             if cached:
                 pc.update(hits=hm[0], misses=hm[1], cache=cache.stats)
             st = getattr(eng, "serve_stats", {})
