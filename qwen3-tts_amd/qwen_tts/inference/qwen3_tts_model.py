@@ -304,7 +304,7 @@ class Qwen3TTSModel:
         self._output_format(sample_rate, pcm_format)
         input_ids, ref_ids, vcp, languages = self._voice_clone_inputs(text, language, ref_audio, ref_text,
                                                                       x_vector_only_mode, voice_clone_prompt)
-        steps = _prosody.request_steps(speed, pitch, volume_gain_db, len(input_ids))
+        steps = _prosody.steps(speed, pitch, volume_gain_db, len(input_ids))
         codes, _ = self.model.generate(input_ids=input_ids, ref_ids=ref_ids, voice_clone_prompt=vcp, languages=languages,
                                        non_streaming_mode=non_streaming_mode,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
@@ -416,7 +416,7 @@ class Qwen3TTSModel:
         self._validate_languages(languages)
         input_ids = self._tokenize_texts([self._build_assistant_text(t) for t in texts])
         ins_ids = [None if not x else self._tokenize_texts([self._build_instruct_text(x)])[0] for x in instructs]
-        steps = _prosody.request_steps(speed, pitch, volume_gain_db, len(input_ids))
+        steps = _prosody.steps(speed, pitch, volume_gain_db, len(input_ids))
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        non_streaming_mode=non_streaming_mode, prefix_cache=prefix_cache,
                                        **self._merge_generate_kwargs(n_requests=len(input_ids), **kwargs))
@@ -459,7 +459,7 @@ class Qwen3TTSModel:
         generate_voice_clone."""
         self._output_format(sample_rate, pcm_format)
         input_ids, ins_ids, languages, speakers = self._custom_voice_inputs(text, speaker, language, instruct)
-        steps = _prosody.request_steps(speed, pitch, volume_gain_db, len(input_ids))
+        steps = _prosody.steps(speed, pitch, volume_gain_db, len(input_ids))
         codes, _ = self.model.generate(input_ids=input_ids, instruct_ids=ins_ids, languages=languages,
                                        speakers=speakers, non_streaming_mode=non_streaming_mode,
                                        prefix_cache=prefix_cache,

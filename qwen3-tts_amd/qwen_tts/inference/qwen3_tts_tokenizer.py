@@ -100,7 +100,7 @@ class Qwen3TTSTokenizer:
         device before the host copy (qwen_tts.PcmResampler.one_shot), float32 or int16, and the requested rate.
         _cut (generate_voice_clone): per wav None or (R, T), dropping its first int(R / T * len) samples before the
         resampler sees it.  _steps (the generate_* wrappers' speed, pitch and gain): per wav its
-        entry of prosody.request_steps(), applied after the cut and before the resampler (PcmTempo.one_shot, then
+        (S, T, db) of prosody.steps(), applied after the cut and before the resampler (PcmTempo.one_shot, then
         PcmProsody.one_shot)."""
         fmt = _resample.output_format(sample_rate, pcm_format, self.get_output_sample_rate())
         if hasattr(encoded, "audio_codes"):
@@ -128,13 +128,11 @@ class Qwen3TTSTokenizer:
                 if _steps is not None:
                     tp, pp = _tempo.PcmTempo(1, self.device), None
                     done = []
-                    for w, step in zip(wavs, _steps):
-                        S, pro = _prosody.split_step(step)
-                        T, db = (S, 0.0) if pro is None else pro
+                    for w, (S, T, db) in zip(wavs, _steps):
                         n, w = int(w.shape[0]), w.to(torch.float32)
                         if T != 100:
                             w = tp.one_shot(w, T)
-                        if pro is not None:
+                        if T != S or db != 0:
                             pp = pp or _prosody.PcmProsody(1, self.device)
                             w = pp.one_shot(w, T, S, db, cap=_tempo.out_len(n, S))
                         done.append(w)

@@ -39,8 +39,7 @@ class LiveRequest:
     frame_cap: Optional[int] = None
     sampling: dict = field(default_factory=dict)
     ref_ids: Optional[List[int]] = None  # a voice-clone (ICL) request's reference text (serve_live(voice_cache=...))
-    speed_step: int = 100  # the request's speaking rate in hundredths (tempo.speed_steps)
-    prosody: Optional[tuple] = None  # (T, db) of a request with a pitch or a gain (prosody.steps), else None
+    step: tuple = (100, 100, 0.0)  # (S, T, db): its speaking rate, tempo step and gain (prosody.steps)
 
 
 class RequestQueue:
@@ -87,8 +86,8 @@ class RequestQueue:
         reference codes), as generate() takes them; the loop serves such a request when it was given a voice_cache.
         speed: the request's speaking rate, 0.5 to 2.0.  pitch / volume_gain_db: its pitch in semitones,
         -12 to 12, and its gain in dB, -96 to 16."""
-        from .prosody import request_steps, split_step
-        step, pro = split_step((request_steps(speed, pitch, volume_gain_db, 1) or [100])[0])
+        from .prosody import steps
+        step = (steps(speed, pitch, volume_gain_db, 1) or [LiveRequest.step])[0]
         unknown = set(sampling) - set(SAMPLING_DEFAULTS)
         if unknown:
             raise TypeError(f"submit() got unexpected keyword arguments {sorted(unknown)}")
@@ -104,7 +103,7 @@ class RequestQueue:
             self._next += 1
             self._new.append(LiveRequest(i, ids, ins, language, speaker, voice_clone_prompt, bool(non_streaming_mode),
                                          bool(open_text), None if frame_cap is None else int(frame_cap),
-                                         {**SAMPLING_DEFAULTS, **sampling}, ref, step, pro))
+                                         {**SAMPLING_DEFAULTS, **sampling}, ref, step))
             self._live.add(i)
             if open_text:
                 self._open[i] = True

@@ -13,10 +13,10 @@ import torch
 from . import kernels as K
 from .prefix import PrefixCache, PrefixPlan
 from .resample import PcmResampler, output_format
-from .prosody import request_steps, split_step
+from .prosody import steps as prosody_steps
 from .tempo import PcmOutput
 from .talker import MIN_NEW_TOKENS, GenParams, HandoffWatch, TalkerEngine
-from .voice import VoiceCache, boundary_skip, check_codes, joint_walk, plan_feed
+from .voice import VoiceCache, boundary_skip, check_codes, feed_span, joint_walk, plan_feed
 
 
 class _Runs:
@@ -462,7 +462,7 @@ class TTSModel:
         at 0 / 0 keeps the default's bits, and with every request there nothing is built.  speed divided by the pitch
         ratio must lie in [0.5, 2.0].  The stateless left_context form does not serve them."""
         fmt = self._output_format(sample_rate, pcm_format)
-        steps = request_steps(speed, pitch, volume_gain_db, 0 if input_ids is None else len(input_ids))
+        steps = prosody_steps(speed, pitch, volume_gain_db, 0 if input_ids is None else len(input_ids))
         self._voice_bind(voice_cache)
         lens = self._prefix_bind(prefix_cache)
         if fmt is not None and left_context is not None:
@@ -471,30 +471,25 @@ class TTSModel:
         if steps is not None and left_context is not None:
             raise NotImplementedError("stream(left_context=...) with speed, pitch or volume_gain_db: use the default "
                                       "stateful stream")
+        # GenParams' arguments, in its order: it validates them, so each route builds it where it always raised
+        sampling = (max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
+                    subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
         if text_feed is not None:
             yield from self._stream_fed(text_feed, input_ids, instruct_ids, voice_clone_prompt, languages, speakers,
                                         non_streaming_mode, left_context, max_batch, first_chunk_frames, chunk_frames,
-                                        use_graph,
-                                        GenParams(max_new_tokens, do_sample, top_k, top_p, temperature,
-                                                  subtalker_dosample, subtalker_top_k, subtalker_top_p,
-                                                  subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos,
-                                                  seed), fmt, prefix_cache, steps)
+                                        use_graph, GenParams(*sampling), fmt, prefix_cache, steps)
             return
         if max_batch is not None and input_ids is not None and len(input_ids) > int(max_batch):
             if left_context is not None:
                 raise NotImplementedError("stream(left_context=...) with max_batch: use the default stateful stream")
             yield from self.serve_stream(
                 input_ids, instruct_ids, ref_ids, voice_clone_prompt, languages, speakers, non_streaming_mode,
-                max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
-                subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed,
-                max_batch=max_batch, first_chunk_frames=first_chunk_frames,
+                *sampling, max_batch=max_batch, first_chunk_frames=first_chunk_frames,
                 chunk_frames=8 if chunk_frames == 48 else chunk_frames, use_graph=use_graph, sample_rate=sample_rate,
                 pcm_format=pcm_format, prefix_cache=prefix_cache, voice_cache=voice_cache, speed=speed,
                 pitch=pitch, volume_gain_db=volume_gain_db, **kwargs)
             return
         dec = self.speech_tokenizer.model
-        up = dec.total_upsample
-        RC, RX = self.REF_CHUNK, self.REF_CTX
         refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
         prefix = None if refs is None or all(r is None for r in refs) else list(refs)
         # voice clone: the reference frames every row starts with are known at submit -- their codec decode starts on
@@ -505,8 +500,7 @@ class TTSModel:
             emb, mask, trail, pad = self.build_prompts(input_ids, languages, speakers, instruct_ids,
                                                        non_streaming_mode, voice_clone_prompt, ref_ids, lens_out=lens)
             plan = self._prefix_plan(prefix_cache, instruct_ids, voice_clone_prompt, lens)
-            gp = GenParams(max_new_tokens, do_sample, top_k, top_p, temperature, subtalker_dosample, subtalker_top_k,
-                           subtalker_top_p, subtalker_temperature, eos_token_id, repetition_penalty, ignore_eos, seed)
+            gp = GenParams(*sampling)
             gp.check_rows(emb.shape[0])
         except BaseException:
             # the side-stream reference decode holds a pooled codec slot: hand it back before the error propagates
@@ -516,11 +510,6 @@ class TTSModel:
             raise
         eos = self.engine.tc["codec_eos_token_id"]
         B = emb.shape[0]
-        emitted = 0                       # windows [0, emitted) decoded for every row
-        end = [None] * B                  # frame count of each row once its EOS is seen
-        cap = [None] * B                  # one-shot sample count (1920 x #nonzero cb0) once the row has ended
-        done = [False] * B
-        cum = [0] * B                     # samples emitted per row
         # chunk sizes double from first_chunk_frames up to chunk_frames: each chunk's audio (80 ms per frame) covers
         # the generation of the next one (~3 ms per frame), so playback started at the first packet never starves
         if left_context is None:
@@ -530,6 +519,13 @@ class TTSModel:
         if prefix is not None:
             raise NotImplementedError("stream(left_context=...) with voice-clone reference codes (ICL): use the "
                                       "default stateful stream")
+        up = dec.total_upsample
+        RC, RX = self.REF_CHUNK, self.REF_CTX
+        emitted = 0                       # windows [0, emitted) decoded for every row
+        end = [None] * B                  # frame count of each row once its EOS is seen
+        cap = [None] * B                  # one-shot sample count (1920 x #nonzero cb0) once the row has ended
+        done = [False] * B
+        cum = [0] * B                     # samples emitted per row
         it = self.engine.decode_iter(emb, mask, trail, pad, gp, use_graph=use_graph, every=chunk_frames,
                                      first=first_chunk_frames + 1, grow=True, prefix=plan)
         for sessions, frames, final in it:
@@ -653,7 +649,7 @@ class TTSModel:
         codec state behind the voice's reference frames from the cache (built on a miss on a one-row stream of its
         own), so a request's first chunk is 1920 x first_chunk_frames - 555 samples as for any other request."""
         fmt = self._output_format(sample_rate, pcm_format)
-        steps = request_steps(speed, pitch, volume_gain_db, 0 if input_ids is None else len(input_ids))
+        steps = prosody_steps(speed, pitch, volume_gain_db, 0 if input_ids is None else len(input_ids))
         voice = self._voice_bind(voice_cache)
         refs = voice_clone_prompt.get("ref_code") if voice_clone_prompt is not None else None
         if voice is None and refs is not None and any(r is not None for r in refs):
@@ -681,93 +677,20 @@ class TTSModel:
         """The codec half of serve_stream() and serve_live(): consumes the talker's (session, report) items
         (TalkerEngine.serve_iter / serve_live_iter) and yields (request, pcm, last).  A row without new frames in a
         report -- idle, or held -- rides along.  An item (None, [requests]) names requests that end without audio.
-        voice (a VoiceCache) selects the route that also serves requests with reference codes, ref_of(request) ->
-        its reference codes or None (_serve_codec_voice).  step_of(request) -> its speed step, asked once
-        when the request takes its slot; the tempo stage is built when the first request with another rate than 1.0
-        arrives (_slot_output), so a call without one runs the default path."""
-        if voice is not None:
-            yield from self._serve_codec_voice(reports, B, first, every, fmt, voice, ref_of, step_of)
-            return
-        dec = self.speech_tokenizer.model
-        up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
-        caps = sorted({first, every})  # feed capacities (one captured codec graph each)
-        dev = self.device
-        rs = dec.row_stream(B, RX + RC, caps[-1])
-        out = None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, dev)
-        rows_ix = torch.arange(B, device=dev)[:, None]
-        req = [-1] * B        # request in each slot, as the codec has seen it
-        discard = [0] * B     # samples of the slot's decode still to drop (a restarted chunk's context)
-        cum = [0] * B         # samples handed out for the slot's request
-        nz = [0] * B          # nonzero cb0 among the request's final frames
-        try:
-            for s, report in reports:
-                if s is None:
-                    for i in report:
-                        yield i, torch.zeros(0, dtype=torch.int16 if fmt is not None and fmt[1] == "s16"
-                                             else torch.float32, device=dev), True
-                    continue
-                # per slot: the frames to feed, and the positions in that list at which the row (re)starts
-                todo, marks, ended = [[] for _ in range(B)], [{} for _ in range(B)], [False] * B
-                for b, r in enumerate(report):
-                    if r is None:
-                        continue
-                    i, lo, f, ended[b], nzb = r
-                    if req[b] != i:
-                        req[b], discard[b], cum[b], nz[b] = i, 0, 0, 0
-                        out = self._slot_output(out, b, 100 if step_of is None else step_of(i), fmt, B)
-                    nz[b] += nzb
-                    # a frame that opens a reference chunk begins the row, after chunk 0 on the 25 context frames
-                    todo[b], mk = joint_walk(0, lo, f, RC, RX)
-                    marks[b] = {k: c * up for k, c in mk.items()}
-                    if ended[b] and not todo[b]:  # nothing new: the request's audio was complete already
-                        if out is not None:  # what the filter still holds back
-                            yield i, out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b], True
-                            continue
-                        yield i, torch.zeros(0, device=dev), True
-                at = [0] * B
-                while any(at[b] < len(todo[b]) for b in range(B)):
-                    nrow, begin = [0] * B, [0] * B
-                    for b in range(B):  # (a restart opens a feed of its own)
-                        nrow[b], begin[b] = plan_feed(todo[b], marks[b], at[b], caps[-1])
-                    n = next(c for c in caps if c >= max(nrow))
-                    ix = torch.tensor([todo[b][at[b]:at[b] + nrow[b]] + [0] * (n - nrow[b]) for b in range(B)],
-                                      dtype=torch.long).pin_memory().to(dev, non_blocking=True)
-                    pcm = rs.feed(s.codes[rows_ix, ix], nrow, begin)
-                    pend = []  # (slot, first sample, samples, last) of this feed, for the resampler's one launch
-                    for b in range(B):
-                        if not nrow[b]:
-                            continue
-                        if begin[b]:
-                            discard[b] = marks[b][at[b]]
-                        at[b] += nrow[b]
-                        lo_s, hi_s = 555 if begin[b] else 0, up * nrow[b]
-                        d = min(discard[b], hi_s - lo_s)
-                        discard[b] -= d
-                        lo_s += d
-                        last = ended[b] and at[b] == len(todo[b])
-                        if ended[b]:  # the reference's length rule: 1920 x #nonzero cb0 of the whole request
-                            hi_s = min(hi_s, lo_s + max(up * nz[b] - cum[b], 0))
-                        if hi_s > lo_s or last:
-                            cum[b] += hi_s - lo_s
-                            if out is not None:
-                                pend.append((b, lo_s, hi_s - lo_s, last))
-                                continue
-                            yield req[b], pcm[b, lo_s:hi_s].clone(), last
-                    if pend:
-                        yield from self._resampled(out, pcm, pend, req)
-        finally:
-            rs.close()
-            reports.close()
+        step_of(request) -> its (S, T, db) (prosody.steps), asked once when the request takes its
+        slot; the output stages are built when the first request off the defaults arrives (_slot_output), so a call
+        without one runs the default path.
 
-    def _serve_codec_voice(self, reports, B, first, every, fmt, voice, ref_of, step_of=None):
-        """_serve_codec for calls with a VoiceCache: requests with reference codes are served beside the
-        others.  Request i decodes cat(ref_i, codes_i): its generated frame t sits at joint position R_i + t, and the
-        chunk walk (voice.joint_walk), the restarts and the 1920 x #nonzero-cb0 length rule run over joint positions.
+        voice (a VoiceCache): requests with reference codes are served beside the others, ref_of(request)
+        -> its reference codes or None.  Request i decodes cat(ref_i, codes_i): its generated frame t sits at joint
+        position R_i + t, and the chunk walk (voice.joint_walk), the restarts and the 1920 x #nonzero-cb0 length rule
+        (voice.feed_span) run over joint positions; without a voice cache R_i = 0 and they are the plain request's.
         In the first report of its slot the request's voice entry is looked up or built (VoiceCache.get: on a miss
         the reference frames are decoded on a one-row stream of their own, never through this stream's feeds), and
         the row adopts the entry's state -- all rows adopting in that report in one qt_codec_row_state launch.  The
-        code window of every feed is assembled on the device from the joint positions (qt_codec_feed_codes), so a
-        restart's 25 context frames come from reference and / or generated frames alike."""
+        code window of every feed is then assembled on the device from the joint positions (qt_codec_feed_codes), so
+        a restart's 25 context frames come from reference and / or generated frames alike; a call without a voice
+        cache gathers it from the session's codes by index."""
         dec = self.speech_tokenizer.model
         up, RC, RX = dec.total_upsample, self.REF_CHUNK, self.REF_CTX
         caps = sorted({first, every})  # feed capacities (one captured codec graph each)
@@ -781,18 +704,32 @@ class TTSModel:
         nz = [0] * B          # nonzero cb0 among the request's reference and final frames
         Rb = [0] * B          # reference frames of the slot's request
         held = [None] * B     # the slot's voice entry (keeps its reference codes alive while the row reads them)
-        # per-slot reference table of qt_codec_feed_codes: pointers and lengths, re-uploaded when a slot's request
-        # changes; the joint positions of a feed go up from pinned memory in stream order
-        ref_ptr = torch.zeros(B, dtype=torch.int64, device=dev)
-        ref_len = torch.zeros(B, dtype=torch.int32, device=dev)
-        empty = torch.int16 if fmt is not None and fmt[1] == "s16" else torch.float32
+        if voice is None:
+            ref_of = None
+            rows_ix = torch.arange(B, device=dev)[:, None]
+        else:
+            # per-slot reference table of qt_codec_feed_codes: pointers and lengths, re-uploaded when a slot's request
+            # changes; the joint positions of a feed go up from pinned memory in stream order
+            ref_ptr = torch.zeros(B, dtype=torch.int64, device=dev)
+            ref_len = torch.zeros(B, dtype=torch.int32, device=dev)
+
+        def window(codes, rows, n):
+            """The feed's code window [B, n, Q]: row b's joint positions rows[b], filler behind them"""
+            fill, dt = (0, torch.long) if voice is None else (-1, torch.int32)
+            pos = torch.tensor([r + [fill] * (n - len(r)) for r in rows], dtype=dt).pin_memory().to(
+                dev, non_blocking=True)
+            if voice is None:
+                return codes[rows_ix, pos]
+            win = torch.empty(B, n, codes.shape[2], dtype=torch.int32, device=dev)
+            K.codec_feed_codes(pos, ref_ptr, ref_len, codes, win)
+            return win
         try:
             for s, report in reports:
                 if s is None:
                     for i in report:
                         if ref_of is not None:
                             ref_of(i)  # (a live loop forgets the request's reference)
-                        yield i, torch.zeros(0, dtype=empty, device=dev), True
+                        yield i, self._empty(fmt), True
                     continue
                 # per slot: the joint positions to feed, and the positions in that list at which the row (re)starts
                 todo, marks, ended = [[] for _ in range(B)], [{} for _ in range(B)], [False] * B
@@ -803,7 +740,7 @@ class TTSModel:
                     i, lo, f, ended[b], nzb = r
                     if req[b] != i:
                         req[b], discard[b], extra[b], cum[b], nz[b], Rb[b], held[b] = i, 0, 0, 0, 0, 0, None
-                        out = self._slot_output(out, b, 100 if step_of is None else step_of(i), fmt, B)
+                        out = self._slot_output(out, b, (100, 100, 0.0) if step_of is None else step_of(i), fmt, B)
                         ref = None if ref_of is None else ref_of(i)
                         if ref is not None and len(ref) > 0:
                             e = held[b] = voice.get(dec, ref)
@@ -816,14 +753,12 @@ class TTSModel:
                                 extra[b] = skip
                         changed = True
                     nz[b] += nzb
+                    # a frame that opens a reference chunk begins the row, after chunk 0 on the 25 context frames
                     todo[b], mk = joint_walk(Rb[b], lo, f, RC, RX)
                     marks[b] = {k: c * up for k, c in mk.items()}
                     if ended[b] and not todo[b]:  # nothing new: the request's audio was complete already
-                        if out is not None:  # what the filter still holds back
-                            yield i, out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b], True
-                            continue
-                        yield i, torch.zeros(0, device=dev), True
-                if changed:
+                        yield i, self._flush_row(out, b, fmt), True
+                if changed and voice is not None:
                     tab = [[0 if held[b] is None else held[b].ref.data_ptr() for b in range(B)], Rb]
                     ref_ptr.copy_(torch.tensor(tab[0], dtype=torch.int64).pin_memory(), non_blocking=True)
                     ref_len.copy_(torch.tensor(tab[1], dtype=torch.int32).pin_memory(), non_blocking=True)
@@ -839,27 +774,17 @@ class TTSModel:
                     for b in range(B):  # (a restart opens a feed of its own)
                         nrow[b], begin[b] = plan_feed(todo[b], marks[b], at[b], caps[-1])
                     n = next(c for c in caps if c >= max(nrow))
-                    pos = torch.tensor([todo[b][at[b]:at[b] + nrow[b]] + [-1] * (n - nrow[b]) for b in range(B)],
-                                       dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-                    win = torch.empty(B, n, s.codes.shape[2], dtype=torch.int32, device=dev)
-                    K.codec_feed_codes(pos, ref_ptr, ref_len, s.codes, win)
-                    pcm = rs.feed(win, nrow, begin)
+                    pcm = rs.feed(window(s.codes, [todo[b][at[b]:at[b] + nrow[b]] for b in range(B)], n), nrow, begin)
                     pend = []  # (slot, first sample, samples, last) of this feed, for the resampler's one launch
                     for b in range(B):
                         if not nrow[b]:
                             continue
-                        if begin[b]:
-                            discard[b], extra[b] = marks[b][at[b]] + extra[b], 0
+                        ctx_s = marks[b][at[b]] if begin[b] else 0
                         at[b] += nrow[b]
-                        lo_s, hi_s = 555 if begin[b] else 0, up * nrow[b]
-                        d = min(discard[b], hi_s - lo_s)
-                        discard[b] -= d
-                        lo_s += d
-                        last = ended[b] and at[b] == len(todo[b])
-                        if ended[b]:  # the reference's length rule: 1920 x #nonzero cb0 of the whole sequence
-                            hi_s = min(hi_s, lo_s + max(up * nz[b] - cum[b], 0))
+                        lo_s, hi_s, last, discard[b], extra[b], cum[b] = feed_span(
+                            begin[b], nrow[b], ctx_s, ended[b], at[b] == len(todo[b]), nz[b], discard[b], extra[b],
+                            cum[b], up)
                         if hi_s > lo_s or last:
-                            cum[b] += hi_s - lo_s
                             if out is not None:
                                 pend.append((b, lo_s, hi_s - lo_s, last))
                                 continue
@@ -901,7 +826,7 @@ class TTSModel:
         fmt = self._output_format(sample_rate, pcm_format)
         voice = self._voice_bind(voice_cache)
         live_refs = {}  # request -> its reference codes, from admission until the codec half has taken them
-        live_steps = {}  # request -> its speed step when it is not 100 (submit(speed=...)), likewise
+        live_steps = {}  # request -> its (S, T, db) where it is off the defaults (submit(speed=...)), likewise
         self._prefix_bind(prefix_cache)
         B = int(max_batch)
         if not 1 <= B <= 64:
@@ -947,14 +872,14 @@ class TTSModel:
                 # (a malformed reference rejects the request here, not in the loop)
                 check_codes(self.speech_tokenizer.model, VoiceCache.codes_array(refs[0]))
                 live_refs[r.id] = refs[0]
-            if r.speed_step != 100 or r.prosody is not None:
-                live_steps[r.id] = r.speed_step if r.prosody is None else (r.speed_step,) + tuple(r.prosody)
+            if r.step != (100, 100, 0.0):
+                live_steps[r.id] = r.step
             return emb[0], trail[0], rgp, plan
 
         yield from self._serve_codec(
             self.engine.serve_live_iter(queue, pad, gp, prepare, slots=B, max_prompt=max_prompt, use_graph=use_graph,
                                         every=every, first=first, text_eos=cfg["tts_eos_token_id"]), B, first, every,
-            fmt, voice, lambda i: live_refs.pop(i, None), lambda i: live_steps.pop(i, 100))
+            fmt, voice, lambda i: live_refs.pop(i, None), lambda i: live_steps.pop(i, (100, 100, 0.0)))
 
     def _output_format(self, sample_rate, pcm_format):
         """The streams' output format, validated before anything is allocated: None = the codec's own (24 kHz fp32,
@@ -964,27 +889,37 @@ class TTSModel:
 
     def _output_stage(self, B, fmt, steps):
         """The output stage of a stream of B rows: None for the default output, the resampler for another format, and
-        with speed steps the tempo stage in front of it, and with a pitch or a gain the prosody stage behind that
-        (tempo.PcmOutput).  steps: prosody.request_steps()'s entries."""
+        with steps (prosody.steps(): one (S, T, db) per row) the tempo stage in front of it, and the prosody stage
+        behind that where a row has a pitch or a gain (tempo.PcmOutput)."""
         if steps is not None:
-            S, pro = zip(*(split_step(s) for s in steps))
-            return PcmOutput(B, S, fmt, self.device, prosody=pro if any(v is not None for v in pro) else None)
+            return PcmOutput(B, steps, fmt, self.device)
         return None if fmt is None else PcmResampler(B, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, self.device)
 
     def _slot_output(self, out, b, step, fmt, B):
-        """Slot b of a serving route's output stage `out` takes a new request at speed step `step` (an entry of
-        prosody.request_steps(): with its tempo step and gain where it has a pitch or a gain): its state is reset.
-        The first request at another rate than 1.0, or with a pitch or a gain, puts the stages in front of what there
-        was (the resampler keeps its state; default rows are copied, so requests under way are not disturbed).
-        Returns the stage."""
-        step, pro = split_step(step)
-        if (step != 100 or pro is not None) and not isinstance(out, PcmOutput):
+        """Slot b of a serving route's output stage `out` takes a new request at `step`, its (S, T, db) (an entry of
+        prosody.steps()): its state is reset.  The first request at another rate than 1.0, or with a pitch or a gain,
+        puts the stages in front of what there was (the resampler keeps its state; default rows are copied, so
+        requests under way are not disturbed).  Returns the stage."""
+        if step != (100, 100, 0.0) and not isinstance(out, PcmOutput):
             out = PcmOutput(B, None, fmt, self.device, rs=out)
         if isinstance(out, PcmOutput):
-            out.reset(b, step, pro)
+            out.reset(b, step)
         elif out is not None:
             out.reset(b)
         return out
+
+    def _empty(self, fmt):
+        """A chunk without samples, in the output format's dtype."""
+        return torch.zeros(0, dtype=torch.int16 if fmt is not None and fmt[1] == "s16" else torch.float32,
+                           device=self.device)
+
+    def _flush_row(self, out, b, fmt):
+        """The last chunk of a row whose input was complete already: what its output stage still holds back, by a
+        push that only flushes that row (nothing without a stage)."""
+        if out is None:
+            return self._empty(fmt)
+        B = out.rows
+        return out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b]
 
     @staticmethod
     def _resampled(out, pcm, pend, names=None):
@@ -1167,10 +1102,7 @@ class TTSModel:
                                 HandoffWatch(sessions).check()
                                 unchecked = False
                             done[b] = True
-                            if out is not None:  # what the filter still holds back
-                                yield b, out.push(None, [0] * B, [0] * B, [c == b for c in range(B)])[b], True
-                                continue
-                            yield b, torch.zeros(0, device=codes.device), True
+                            yield b, self._flush_row(out, b, fmt), True
                 if all(done):
                     break
         finally:

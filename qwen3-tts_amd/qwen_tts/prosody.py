@@ -90,52 +90,17 @@ def tempo_step(S, pitch) -> int:
     return T
 
 
-def _numbers(v, n, name, lo, hi, default):
-    if isinstance(v, (list, tuple, np.ndarray)):
-        vals = list(v)
-        if len(vals) != n:
-            raise ValueError(f"{name} has {len(vals)} entries for {n} requests")
-    else:
-        vals = [v] * n
-    out = []
-    for x in vals:
-        if x is None:
-            x = default
-        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
-            raise ValueError(f"{name} must be a number in [{lo:g}, {hi:g}], got {x!r}")
-        x = float(x)
-        if not math.isfinite(x) or not lo <= x <= hi:
-            raise ValueError(f"{name} must be a finite number in [{lo:g}, {hi:g}], got {x!r}")
-        out.append(x)
-    return out
-
-
 def steps(speed, pitch, volume_gain_db, n):
     """Validate a caller's speed, pitch (semitones) and volume_gain_db -- each a number, or one per request -- and
     return one (S, T, db) per request: S = round(100 * speed), T the tempo step, db the gain.  None when every
     request is at 1.0 / 0 / 0 (no stage is built then)."""
     S = _tempo.speed_steps(1.0 if speed is None else speed, n) or [100] * n
-    p = _numbers(pitch, n, "pitch", PITCH_MIN, PITCH_MAX, 0.0)
-    db = _numbers(volume_gain_db, n, "volume_gain_db", DB_MIN, DB_MAX, 0.0)
+    p = _tempo.numbers(pitch, n, "pitch", PITCH_MIN, PITCH_MAX, 0.0)
+    db = _tempo.numbers(volume_gain_db, n, "volume_gain_db", DB_MIN, DB_MAX, 0.0)
     out = [(s, tempo_step(s, pi), d) for s, pi, d in zip(S, p, db)]
     if all(o == (100, 100, 0.0) for o in out):
         return None
     return out
-
-
-def request_steps(speed, pitch, volume_gain_db, n):
-    """What the routes carry per request: None when every request is at the defaults, else one entry per request --
-    the speed step S alone (an int, as tempo.speed_steps gives it) for a request without pitch or gain, which then
-    needs no more than the tempo stage, else (S, T, db)."""
-    if pitch is None and volume_gain_db is None:
-        return None if speed is None else _tempo.speed_steps(speed, n)
-    st = steps(speed, pitch, volume_gain_db, n)
-    return None if st is None else [s if (t == s and d == 0) else (s, t, d) for s, t, d in st]
-
-
-def split_step(step):
-    """An entry of request_steps() -> (S, None or (T, db))"""
-    return (step, None) if isinstance(step, int) else (step[0], tuple(step[1:]))
 
 
 def ready(p: Plan, limited: bool, n_total: int, flush: bool = False, cap=None) -> int:
@@ -249,7 +214,7 @@ class PcmProsody:
             self.plan[row] = plan(T, S)
             self.table[row] = _device_table(self.plan[row], self.device)
         if db is not None:
-            self.db[row] = _numbers(db, 1, "volume_gain_db", DB_MIN, DB_MAX, 0.0)[0]
+            self.db[row] = _tempo.numbers(db, 1, "volume_gain_db", DB_MIN, DB_MAX, 0.0)[0]
         self.taken[row], self.given[row] = 0, 0
         self.fresh[row], self.flushed[row] = True, False
 
@@ -259,58 +224,34 @@ class PcmProsody:
     def push(self, src, offsets, lengths, flush, cap=None):
         import torch
         from . import kernels as K
-        B = self.rows
-        if isinstance(flush, bool):
-            flush = [flush] * B
         if cap is None:
-            cap = [None] * B
-        if not (len(offsets) == len(lengths) == len(flush) == len(cap) == B):
-            raise ValueError(f"push() takes one offset, length, flush and cap per row ({B} rows)")
-        if src is None:  # a call that only flushes
-            if any(lengths):
-                raise ValueError("push(None, ...) takes no samples")
-            src = self.state[0, 0]
-        if src.dtype != torch.float32 or src.device != self.device or src.dim() not in (1, 2) or \
-                (src.numel() and src.stride(-1) != 1):
-            raise ValueError("push() takes an fp32 tensor on the stage's device, 1-D or [rows, L], unit stride")
-        if src.dim() == 2 and src.shape[0] != B:
-            raise ValueError(f"push() takes [rows, L] with rows = {B}, got {tuple(src.shape)}")
-        span = src.shape[-1]
+            cap = [None] * self.rows
+        src, flush, spans = _rs.check_push(self, src, offsets, lengths, flush, self.state[0, 0], cap)
         counts = []
-        for b in range(B):
-            o, n = int(offsets[b]), int(lengths[b])
-            if n < 0 or o < 0 or (n and o + n > span):
-                raise ValueError(f"row {b}: samples [{o}, {o + n}) lie outside the source's {span}")
-            if n and self.flushed[b]:
-                raise ValueError(f"row {b} was flushed: reset() it before its next signal")
+        for b, (_, n) in enumerate(spans):
             if cap[b] is not None and int(cap[b]) < 0:
                 raise ValueError(f"row {b}: cap must not be negative, got {cap[b]}")
-            counts.append(max(0, ready(self.plan[b], self.db[b] > 0, self.taken[b] + n, bool(flush[b]), cap[b])
+            counts.append(max(0, ready(self.plan[b], self.db[b] > 0, self.taken[b] + n, flush[b], cap[b])
                               - self.given[b]))
         out = torch.empty(sum(counts), dtype=torch.float32, device=self.device)
-        outs, table, at = [], [], 0
-        base = src.data_ptr()
-        for b in range(B):
-            o, n, c, p = int(offsets[b]), int(lengths[b]), counts[b], self.plan[b]
-            outs.append(out[at:at + c])
-            row0 = b * src.stride(0) if src.dim() == 2 else 0
+        ptrs, outs = _rs.push_views(src, spans, out, counts)
+        table = []
+        for b, (_, n) in enumerate(spans):
+            p = self.plan[b]
             st_in = None if self.fresh[b] else self.state[self.par[b], b].data_ptr()
             st_out = self.state[self.par[b] ^ 1, b].data_ptr()
             pos0, m_start = self.start_period * p.down, self.start_period * p.up
-            table.append((base + 4 * (row0 + o) if n else None, out.data_ptr() + 4 * at if c else None, st_in, st_out,
-                          self.table[b].data_ptr(), pos0 + self.taken[b], m_start + self.given[b], pos0,
-                          -1 if cap[b] is None else int(cap[b]), n, c, p.up, p.down, p.half, p.taps,
-                          float(gain(self.db[b])), int(self.db[b] > 0), int(bool(flush[b]))))
-            at += c
+            table.append((*ptrs[b], st_in, st_out, self.table[b].data_ptr(), pos0 + self.taken[b],
+                          m_start + self.given[b], pos0, -1 if cap[b] is None else int(cap[b]), n, counts[b], p.up,
+                          p.down, p.half, p.taps, float(gain(self.db[b])), int(self.db[b] > 0), int(flush[b])))
         K.prosody(table)
-        for b in range(B):
-            n = int(lengths[b])
+        for b, (_, n) in enumerate(spans):
             if n:
                 self.taken[b] += n
                 self.par[b] ^= 1
                 self.fresh[b] = False
             self.given[b] += counts[b]
-            self.flushed[b] = self.flushed[b] or bool(flush[b])
+            self.flushed[b] = self.flushed[b] or flush[b]
         self.last = out
         return outs
 

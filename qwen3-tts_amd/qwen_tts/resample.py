@@ -109,6 +109,50 @@ def _device_table(p: Plan, device):
     return _TABLES[key]
 
 
+def check_push(stage, src, offsets, lengths, flush, standin, *more):
+    """What the push() of every stateful stage checks first (PcmResampler, tempo.PcmTempo, prosody.PcmProsody; `stage`
+    has rows, device and flushed).  flush: one bool per row, or one for all; more: the stage's further per-row lists;
+    src None: a call that only flushes, which takes no samples and reads `standin`, a tensor of the stage's.  Returns
+    (src, flush as a list of bools, [(offset, length)] per row)."""
+    import torch
+    B = stage.rows
+    if isinstance(flush, bool):
+        flush = [flush] * B
+    if any(len(v) != B for v in (offsets, lengths, flush) + more):
+        raise ValueError(f"push() takes one entry per row in each of its lists ({B} rows)")
+    if src is None:
+        if any(lengths):
+            raise ValueError("push(None, ...) takes no samples")
+        src = standin
+    if src.dtype != torch.float32 or src.device != stage.device or src.dim() not in (1, 2) or \
+            (src.numel() and src.stride(-1) != 1):
+        raise ValueError("push() takes an fp32 tensor on the stage's device, 1-D or [rows, L], unit stride")
+    if src.dim() == 2 and src.shape[0] != B:
+        raise ValueError(f"push() takes [rows, L] with rows = {B}, got {tuple(src.shape)}")
+    span, spans = src.shape[-1], []
+    for b in range(B):
+        o, n = int(offsets[b]), int(lengths[b])
+        if n < 0 or o < 0 or (n and o + n > span):
+            raise ValueError(f"row {b}: samples [{o}, {o + n}) lie outside the source's {span}")
+        if n and stage.flushed[b]:
+            raise ValueError(f"row {b} was flushed: reset() it before its next signal")
+        spans.append((o, n))
+    return src, [bool(f) for f in flush], spans
+
+
+def push_views(src, spans, out, counts):
+    """Where a push reads and writes: per row (address of its first source sample, or None where it takes none;
+    address of its first output in `out`, or None where it gets none), and the rows' views of `out`, back to back."""
+    base, esz = src.data_ptr(), out.element_size()
+    stride = src.stride(0) if src.dim() == 2 else 0
+    ptrs, outs, at = [], [], 0
+    for b, ((o, n), c) in enumerate(zip(spans, counts)):
+        ptrs.append((base + 4 * (b * stride + o) if n else None, out.data_ptr() + esz * at if c else None))
+        outs.append(out[at:at + c])
+        at += c
+    return ptrs, outs
+
+
 class PcmResampler:
     """`rows` independent streams through one device resampler.
 
@@ -150,49 +194,25 @@ class PcmResampler:
     def push(self, src, offsets, lengths, flush):
         import torch
         from . import kernels as K
-        B, p = self.rows, self.plan
-        if isinstance(flush, bool):
-            flush = [flush] * B
-        if not (len(offsets) == len(lengths) == len(flush) == B):
-            raise ValueError(f"push() takes one offset, length and flush per row ({B} rows)")
-        if src is None:  # a call that only flushes
-            if any(lengths):
-                raise ValueError("push(None, ...) takes no samples")
-            src = self.table.view(-1)
-        if src.dtype != torch.float32 or src.device != self.device or src.dim() not in (1, 2) or \
-                (src.numel() and src.stride(-1) != 1):
-            raise ValueError("push() takes an fp32 tensor on the resampler's device, 1-D or [rows, L], unit stride")
-        if src.dim() == 2 and src.shape[0] != B:
-            raise ValueError(f"push() takes [rows, L] with rows = {B}, got {tuple(src.shape)}")
-        span = src.shape[-1]
-        counts = []
-        for b in range(B):
-            o, n = int(offsets[b]), int(lengths[b])
-            if n < 0 or o < 0 or (n and o + n > span):
-                raise ValueError(f"row {b}: samples [{o}, {o + n}) lie outside the source's {span}")
-            if n and self.flushed[b]:
-                raise ValueError(f"row {b} was flushed: reset() it before its next signal")
-            counts.append(max(0, ready(p, self.pos[b] + n - self.start_pos, bool(flush[b])) - self.emitted(b)))
+        p = self.plan
+        src, flush, spans = check_push(self, src, offsets, lengths, flush, self.table.view(-1))
+        counts = [max(0, ready(p, self.pos[b] + n - self.start_pos, flush[b]) - self.emitted(b))
+                  for b, (_, n) in enumerate(spans)]
         out = torch.empty(sum(counts), dtype=self.dtype, device=self.device)
-        outs, table, at = [], [], 0
-        base, esz = src.data_ptr(), out.element_size()
-        for b in range(B):
-            o, n, c = int(offsets[b]), int(lengths[b]), counts[b]
-            outs.append(out[at:at + c])
-            row0 = b * src.stride(0) if src.dim() == 2 else 0
+        ptrs, outs = push_views(src, spans, out, counts)
+        table = []
+        for b, (_, n) in enumerate(spans):
             hin = None if self.fresh[b] else self.hist[self.par[b], b].data_ptr()
-            table.append((base + 4 * (row0 + o) if n else None, out.data_ptr() + esz * at if c else None, hin,
-                          self.hist[self.par[b] ^ 1, b].data_ptr(), self.pos[b], self.m0[b], n, c, int(bool(flush[b]))))
-            at += c
+            table.append((*ptrs[b], hin, self.hist[self.par[b] ^ 1, b].data_ptr(), self.pos[b], self.m0[b], n,
+                          counts[b], int(flush[b])))
         K.resample(self.table, p.up, p.down, p.half, p.taps, self.H, self.pcm_format, table)
-        for b in range(B):
-            n = int(lengths[b])
+        for b, (_, n) in enumerate(spans):
             if n:
                 self.pos[b] += n
                 self.par[b] ^= 1
                 self.fresh[b] = False
             self.m0[b] += counts[b]
-            self.flushed[b] = self.flushed[b] or bool(flush[b])
+            self.flushed[b] = self.flushed[b] or flush[b]
         return outs
 
     def one_shot(self, x, lengths=None):

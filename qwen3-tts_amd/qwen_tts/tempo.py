@@ -97,25 +97,33 @@ def check_steps(S) -> int:
     return int(S)
 
 
+def numbers(v, n, name, lo, hi, default, span=None):
+    """Validate a caller's per-request value `name` -- a number, or one per request -- and return n floats in
+    [lo, hi], `default` where an entry is None.  span: how the messages write the range."""
+    span = span or f"[{lo:g}, {hi:g}]"
+    if isinstance(v, (list, tuple, np.ndarray)):
+        vals = list(v)
+        if len(vals) != n:
+            raise ValueError(f"{name} has {len(vals)} entries for {n} requests")
+    else:
+        vals = [v] * n
+    out = []
+    for x in vals:
+        if x is None:
+            x = default
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{name} must be a number in {span}, got {x!r}")
+        x = float(x)
+        if not math.isfinite(x) or not lo <= x <= hi:
+            raise ValueError(f"{name} must be a finite number in {span}, got {x!r}")
+        out.append(x)
+    return out
+
+
 def speed_steps(speed, n):
     """Validate a caller's `speed` -- a number, or one per request -- and return one S = round(100 * speed) per
     request, or None when every entry is 1.0 (no stage is built then)."""
-    if isinstance(speed, (list, tuple, np.ndarray)):
-        vals = list(speed)
-        if len(vals) != n:
-            raise ValueError(f"speed has {len(vals)} entries for {n} requests")
-    else:
-        vals = [speed] * n
-    out = []
-    for v in vals:
-        if v is None:
-            v = 1.0
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)):
-            raise ValueError(f"speed must be a number in [0.5, 2.0], got {v!r}")
-        v = float(v)
-        if not math.isfinite(v) or not 0.5 <= v <= 2.0:
-            raise ValueError(f"speed must be a finite number in [0.5, 2.0], got {v!r}")
-        out.append(int(round(100 * v)))
+    out = [int(round(100 * v)) for v in numbers(speed, n, "speed", 0.5, 2.0, 1.0, "[0.5, 2.0]")]
     if all(s == 100 for s in out):
         return None
     return out
@@ -230,52 +238,29 @@ class PcmTempo:
     def push(self, src, offsets, lengths, flush, steps):
         import torch
         from . import kernels as K
+        from .resample import check_push, push_views
         B = self.rows
-        if isinstance(flush, bool):
-            flush = [flush] * B
         if isinstance(steps, int):
             steps = [steps] * B
-        if not (len(offsets) == len(lengths) == len(flush) == len(steps) == B):
-            raise ValueError(f"push() takes one offset, length, flush and step per row ({B} rows)")
-        if src is None:  # a call that only flushes
-            if any(lengths):
-                raise ValueError("push(None, ...) takes no samples")
-            src = self.window
-        if src.dtype != torch.float32 or src.device != self.device or src.dim() not in (1, 2) or \
-                (src.numel() and src.stride(-1) != 1):
-            raise ValueError("push() takes an fp32 tensor on the stage's device, 1-D or [rows, L], unit stride")
-        if src.dim() == 2 and src.shape[0] != B:
-            raise ValueError(f"push() takes [rows, L] with rows = {B}, got {tuple(src.shape)}")
-        span = src.shape[-1]
+        src, flush, spans = check_push(self, src, offsets, lengths, flush, self.window, steps)
         counts, S = [], [0] * B
-        for b in range(B):
-            o, n = int(offsets[b]), int(lengths[b])
-            if n < 0 or o < 0 or (n and o + n > span):
-                raise ValueError(f"row {b}: samples [{o}, {o + n}) lie outside the source's {span}")
-            if n and self.flushed[b]:
-                raise ValueError(f"row {b} was flushed: reset() it before its next signal")
+        for b, (_, n) in enumerate(spans):
             S[b] = check_steps(steps[b])
             if self.step[b] is not None and S[b] != self.step[b]:
                 raise ValueError(f"row {b} runs at step {self.step[b]}: reset() it before it changes to {steps[b]}")
-            counts.append(max(0, ready(S[b], self.taken[b] + n, bool(flush[b])) - self.given[b]))
+            counts.append(max(0, ready(S[b], self.taken[b] + n, flush[b]) - self.given[b]))
         out = torch.empty(sum(counts), dtype=torch.float32, device=self.device)
-        outs, table, at = [], [], 0
-        base = src.data_ptr()
+        ptrs, outs = push_views(src, spans, out, counts)
+        table = []
         sb = self.STATE_I64 * 8
-        for b in range(B):
-            o, n, c = int(offsets[b]), int(lengths[b]), counts[b]
-            outs.append(out[at:at + c])
-            row0 = b * src.stride(0) if src.dim() == 2 else 0
+        for b, (_, n) in enumerate(spans):
             a0 = a(self.start_block, S[b])
             st_in = None if self.fresh[b] else self.state.data_ptr() + sb * (self.par[b] * B + b)
             st_out = self.state.data_ptr() + sb * ((self.par[b] ^ 1) * B + b)
-            table.append((base + 4 * (row0 + o) if n else None, out.data_ptr() + 4 * at if c else None, st_in, st_out,
-                          a0 + self.taken[b], self.start_block + self.given[b] // HS, self.start_block, n, c, S[b],
-                          int(bool(flush[b]))))
-            at += c
+            table.append((*ptrs[b], st_in, st_out, a0 + self.taken[b], self.start_block + self.given[b] // HS,
+                          self.start_block, n, counts[b], S[b], int(flush[b])))
         K.tempo(self.window, table)
-        for b in range(B):
-            n = int(lengths[b])
+        for b, (_, n) in enumerate(spans):
             if n or counts[b] or flush[b]:
                 self.step[b] = S[b]
             if n:
@@ -284,7 +269,7 @@ class PcmTempo:
                     self.par[b] ^= 1
                     self.fresh[b] = False
             self.given[b] += counts[b]
-            self.flushed[b] = self.flushed[b] or bool(flush[b])
+            self.flushed[b] = self.flushed[b] or flush[b]
         self.last = out
         return outs
 
@@ -302,26 +287,26 @@ class PcmOutput:
     most three launches per push for all rows; every stage's counts are its host rule's, so its output feeds the next
     as a 1-D source without a synchronisation."""
 
-    def __init__(self, rows, steps, fmt, device, rs=None, prosody=None):
-        """fmt: resample.output_format()'s (Plan, pcm_format) or None; rs: a PcmResampler of that format to go on
-        with (its rows keep their state) instead of a new one; prosody: per row None or (T, db), the row's tempo
-        step and gain (prosody.steps) -- the pitch stage is built with the first row that has one."""
+    def __init__(self, rows, steps, fmt, device, rs=None):
+        """steps: per row its (S, T, db) -- speed step, tempo step and gain (prosody.steps) -- or None: every row at
+        (100, 100, 0.0); the pitch stage is built with the first row that has T != S or a gain.  fmt:
+        resample.output_format()'s (Plan, pcm_format) or None; rs: a PcmResampler of that format to go on with (its
+        rows keep their state) instead of a new one."""
         from .resample import PcmResampler
         self.rows = int(rows)
         self.tempo = PcmTempo(rows, device)
         if rs is None and fmt is not None:
             rs = PcmResampler(rows, fmt[0].sample_rate, fmt[1], fmt[0].in_rate, device)
         self.rs = rs
-        self.steps = [100] * self.rows if steps is None else [check_steps(s) for s in steps]
-        self.tsteps = list(self.steps)   # the steps the tempo stage runs at: T of prosody.py, S without a pitch
+        self.steps = [100] * self.rows    # S: what the output's length follows
+        self.tsteps = [100] * self.rows   # the steps the tempo stage runs at: T of prosody.py, S without a pitch
         self.pro = None
-        for b, v in enumerate(prosody or ()):
-            self._prosody(b, v)
+        for b, st in enumerate(steps or ()):
+            self._step(b, st)
 
-    def _prosody(self, row, v):
-        S = self.steps[row]
-        T, db = (S, 0.0) if v is None else v
-        self.tsteps[row] = check_steps(T)
+    def _step(self, row, step):
+        S, T, db = step
+        self.steps[row], self.tsteps[row] = check_steps(S), check_steps(T)
         if self.pro is None:
             if T == S and db == 0:
                 return
@@ -330,13 +315,11 @@ class PcmOutput:
             self.pro = PcmProsody(self.rows, self.tempo.device)
         self.pro.reset(row, T, S, db)
 
-    def reset(self, row, step=None, prosody=None):
+    def reset(self, row, step=(100, 100, 0.0)):
         self.tempo.reset(row)
         if self.rs is not None:
             self.rs.reset(row)
-        if step is not None:
-            self.steps[row] = check_steps(step)
-        self._prosody(row, prosody)
+        self._step(row, step)
 
     def push(self, src, offsets, lengths, flush):
         if isinstance(flush, bool):

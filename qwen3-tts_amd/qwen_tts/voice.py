@@ -6,7 +6,8 @@ That state depends on the reference codes alone.  `VoiceCache` keeps it per voic
 `codec.RowCodecStream` of its own (never through the serving stream's feeds), exported with qt_codec_row_state, and
 adopted into the request's row -- one launch for all rows that adopt in a report.
 
-`joint_walk` is the chunk walk both the serving loop and the warm-up follow.  The bookkeeping and the walk touch no
+`joint_walk` is the chunk walk both the serving loop and the warm-up follow, `plan_feed` and `feed_span` the loop's
+choice of a feed's frames and of the samples a row hands out from it.  The bookkeeping and the walk touch no
 device API, so this module imports (and is tested) without a GPU; only building an entry needs one.
 """
 from __future__ import annotations
@@ -59,6 +60,26 @@ def boundary_skip(R: int, chunk: int = REF_CHUNK, tail: int = TAIL) -> Tuple[boo
     generated frame opens chunk k itself: nothing to adopt, and tail k samples go after the context's."""
     k = R // chunk
     return (True, tail * (k + 1)) if R % chunk else (False, tail * k)
+
+
+def feed_span(begin, nrow: int, ctx_s: int, ended, final, nz: int, discard: int, extra: int, cum: int, up: int,
+              tail: int = TAIL) -> Tuple[int, int, bool, int, int, int]:
+    """The samples a row hands out from one feed of nrow frames, whose decode is [0, up * nrow) of the feed's PCM row
+    (a feed that begins has nothing in its first `tail` samples).  begin: the row (re)starts with this feed, on ctx_s
+    samples of context (the feed's mark, in samples) whose output is dropped, and `extra` more at the request's first
+    begin (boundary_skip without adoption); discard: samples still to drop from earlier feeds; ended: the request's
+    frames are all known, nz nonzero cb0 among reference and generated ones, so the 1920 x #nonzero-cb0 length rule
+    cuts at up * nz; final: this is the last feed of the row's list; cum: the sample of the request's whole decode the
+    row has reached.  Returns (lo, hi, last, discard, extra, cum): the span [lo, hi) to hand out, whether it is the
+    request's last, and the new state."""
+    if begin:
+        discard, extra = ctx_s + extra, 0
+    lo, hi = tail if begin else 0, up * nrow
+    d = min(discard, hi - lo)
+    lo += d
+    if ended:
+        hi = min(hi, lo + max(up * nz - cum, 0))
+    return lo, hi, bool(ended and final), discard - d, extra, cum + hi - lo
 
 
 @dataclass

@@ -31,6 +31,29 @@ def test_ids_are_consecutive_and_requests_arrive_once_in_order():
         q.submit([1, 2, 3, 4], frame_cap=0)
 
 
+def test_a_requests_step_is_the_tuple_of_prosody_steps():
+    """speed, pitch and gain reach the loop as prosody.steps()'s (S, T, db), checked at submit"""
+    from qwen_tts import prosody as P
+    from qwen_tts.live import LiveRequest
+    q = _queue()
+    vals = ((None, None, None), (1.0, 0, 0.0), (1.25, None, None), (1.5, 2, None), (None, -7, 6), (0.8, 3, -4.5),
+            (None, None, 16))
+    for s, p, d in vals:
+        q.submit([1, 2, 3, 4], speed=s, pitch=p, volume_gain_db=d)
+    new = q.drain()[0]
+    assert LiveRequest(0, [1]).step == (100, 100, 0.0)
+    for r, (s, p, d) in zip(new, vals):
+        assert type(r.step) is tuple and r.step == (P.steps(s, p, d, 1) or [(100, 100, 0.0)])[0], r.id
+    assert [r.step for r in new[:5]] == [(100, 100, 0.0), (100, 100, 0.0), (125, 125, 0.0), (150, 134, 0.0),
+                                         (100, 150, 6.0)]
+    for bad in (dict(pitch=13), dict(volume_gain_db=17), dict(pitch=True), dict(speed=0.5, pitch=2), dict(speed=2.5),
+                dict(speed=[1.0, 1.0])):
+        with pytest.raises(ValueError):
+            q.submit([1, 2, 3, 4], **bad)
+    assert q.drain()[0] == []  # a refused submit queues nothing and takes no id
+    assert q.submit([1, 2, 3, 4]) == len(vals)
+
+
 def test_push_before_admission_and_no_push_after_close_text():
     import torch
     q = _queue()

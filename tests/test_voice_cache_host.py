@@ -1,11 +1,11 @@
 """CPU-only: the voice cache's host side (qwen_tts/voice.py) -- VoiceCache bookkeeping with stub entries,
 and the joint-position chunk walk of the serving loop against a plain restatement of the reference's chunked decode of
-cat(ref, codes)."""
+cat(ref, codes), down to the samples a row hands out from every feed (feed_span)."""
 import numpy as np
 import pytest
 import torch
 
-from qwen_tts.voice import VoiceCache, VoiceEntry, boundary_skip, joint_walk, plan_feed
+from qwen_tts.voice import VoiceCache, VoiceEntry, boundary_skip, feed_span, joint_walk, plan_feed
 
 UP, TAIL, RC, RX = 1920, 555, 300, 25
 
@@ -152,3 +152,109 @@ def test_boundary_skip_values():
     assert boundary_skip(7) == (True, 555) and boundary_skip(299) == (True, 555)
     assert boundary_skip(300) == (False, 555) and boundary_skip(301) == (True, 1110)
     assert boundary_skip(600) == (False, 1110)
+
+
+CH, CX = 5, 2  # a small geometry for the sample accounting: chunks of 5 frames, 2 frames of context
+
+
+def _one_shot_labels(T):
+    """The chunked decode of joint frames [0, T) at chunk CH / context CX, every sample labelled 1920 * (the frame it
+    is decoded from) + its offset: chunk [start, end) decodes its context frames and its own, loses the last 555
+    samples and drops the context's."""
+    out = []
+    for start in range(0, T, CH):
+        end = min(start + CH, T)
+        c = CX if start - CX > 0 else start
+        frames = np.arange(start - c, end)
+        q = np.arange(UP * c, UP * len(frames) - TAIL)
+        out.append(frames[q // UP] * UP + q % UP)
+    return np.concatenate(out) if out else np.zeros(0, np.int64)
+
+
+class _FakeRow:
+    """One row of the incremental decoder, as the serving loop sees it: after m frames since its begin it has produced
+    1920 m - 555 samples of their decode, and a feed of n frames returns [1920 n] with what those frames added at its
+    end -- so nothing in the first 555 of a feed that begins (-1 here)."""
+
+    def __init__(self, fed=()):
+        self.fed = list(fed)
+
+    def feed(self, positions, begin):
+        if begin:
+            self.fed = []
+        assert begin or self.fed, "a row that has no state must begin"
+        q = UP * len(self.fed) - TAIL + np.arange(UP * len(positions))
+        self.fed += positions
+        return np.where(q >= 0, np.asarray(self.fed)[np.maximum(q, 0) // UP] * UP + q % UP, -1)
+
+
+def _serve(R, F, caps, step, cb0):
+    """One slot's walk through a request of F generated frames behind R reference ones, reported `step` frames at a
+    time, as TTSModel._serve_codec runs it; returns (the chunks handed out, their last flags)."""
+    adopt, skip = boundary_skip(R, CH, TAIL)
+    row = _FakeRow()
+    if adopt:  # the voice entry's state: chunk R // CH of the reference, fed from its context up to frame R
+        start = R // CH * CH
+        row = _FakeRow(range(start - (CX if start - CX > 0 else start), R))
+    discard, extra = (skip, 0) if adopt else (0, skip)
+    cum, nz = UP * R, sum(cb0[:R])
+    chunks, lasts = [], []
+    for lo in range(0, F, step):
+        f = min(lo + step, F)
+        ended = f == F
+        nz += sum(cb0[R + lo:R + f])
+        todo, mk = joint_walk(R, lo, f, CH, CX)
+        marks = {k: c * UP for k, c in mk.items()}
+        at = 0
+        while at < len(todo):
+            n, begin = plan_feed(todo, marks, at, caps[-1])
+            assert 1 <= n and any(c >= n for c in caps)
+            pcm = row.feed(todo[at:at + n], begin)
+            ctx_s = marks[at] if begin else 0
+            at += n
+            lo_s, hi_s, last, discard, extra, cum = feed_span(begin, n, ctx_s, ended, at == len(todo), nz, discard,
+                                                              extra, cum, UP, TAIL)
+            assert (TAIL if begin else 0) <= lo_s <= hi_s <= UP * n
+            if hi_s > lo_s or last:
+                chunks.append(pcm[lo_s:hi_s])
+                lasts.append(last)
+    return chunks, lasts
+
+
+@pytest.mark.parametrize("F", [1, 4, 11])
+@pytest.mark.parametrize("R", [0, 3, 5, 7])
+def test_feed_span_hands_out_the_one_shot_samples(R, F):
+    """joint_walk + plan_feed + boundary_skip + feed_span against a decoder that labels its samples: whatever the
+    feed capacities and the reports' sizes, a request gets wav[1920 R : 1920 nz] of the chunked decode of its R + F
+    joint frames, in order, and exactly one last, on its final chunk.
+
+    The length rule 1920 x #nonzero-cb0 is known with the request's last report only, and what a stream has handed
+    out stays handed out: where zero cb0 make 1920 nz fall below the samples that existed before the last report
+    (all of the decode of the T' joint frames known until then, 1920 T' - 555 ceil(T' / chunk)), the audio ends
+    there instead.  With every cb0 nonzero, and with the request in one report, that is the rule itself."""
+    T = R + F
+    wav = _one_shot_labels(T)
+    whole = UP * T - TAIL * -(-T // CH)
+    assert len(wav) == whole
+    for zeros in ((), {0, T - 1}):  # every cb0 nonzero; two zero ones (one, where there is one frame)
+        cb0 = [int(j not in zeros) for j in range(T)]
+        nz = sum(cb0)
+        for caps in ((1, 8), (2, 3)):
+            for step in (1, 3, F):
+                before = R + (F - 1) // step * step  # joint frames known before the last report
+                end = max(UP * nz, UP * before - TAIL * -(-before // CH))
+                want = wav[:end][UP * R:]
+                if not zeros or step == F:
+                    assert len(want) == max(0, min(whole, UP * nz) - UP * R)
+                chunks, lasts = _serve(R, F, caps, step, cb0)
+                assert lasts.count(True) == 1 and lasts[-1] is True, (caps, step, lasts)
+                got = np.concatenate(chunks)
+                assert got.shape == want.shape and (got == want).all(), (caps, step, len(zeros))
+
+
+def test_feed_span_plain_request_is_the_no_reference_case():
+    """R = 0 without a voice cache: no adoption, nothing extra, and the first feed drops its 555 alone"""
+    assert boundary_skip(0, CH, TAIL) == (False, 0)
+    assert feed_span(1, 1, 0, False, True, 1, 0, 0, 0, UP) == (TAIL, UP, False, 0, 0, UP - TAIL)
+    assert feed_span(0, 2, 0, True, True, 3, 0, 0, UP - TAIL, UP) == (0, 2 * UP, True, 0, 0, 3 * UP - TAIL)
+    assert feed_span(0, 2, 0, True, False, 2, 0, 0, UP - TAIL, UP) == (0, UP + TAIL, False, 0, 0, 2 * UP)
