@@ -501,27 +501,80 @@ class Session:
         self.stashed = 0   # rows whose stash holds their current state (held in the last replay, not refilled since)
         self.cp = CPLane(self, eng)
 
+    def idle(self, b: int):
+        """Row b decodes no request: from here in stream order it emits EOS, until a prefill takes the row."""
+        self.finished[b:b + 1].fill_(1)
 
-class TextGate:
-    """The host's account of a streamed request's trailing text: which positions of Session.trailing are
-    written, per row, and therefore which frame replays may be queued.  The host is the authority: the frame kernels
-    read whatever the buffer holds.  Used by the thread that runs the generator only; other threads touch the feed."""
+
+class TextAccount:
+    """The host's account of the trailing text of a session's rows: per row, which positions of
+    Session.trailing are present, written, and whether the end of text is.  The host is the authority: the frame
+    kernels read whatever the buffer holds.  Plain Python, no device state; one thread uses it."""
 
     # Tokens are projected a little ahead of the frames, not all at once: a backlog of 8 x 200 tokens is 100 appends,
     # which in front of the first replay cost 2.1 ms of a 6.2 ms first packet.  When a row's next unwritten position
     # is fewer than LOW frames ahead of the replay about to be queued, every row is written up to AHEAD frames ahead.
     LOW, AHEAD = 8, 24
 
+    def __init__(self, rows: int, cap: int):
+        self.cap = int(cap)                         # the frame cap: no frame reads a position at or past it
+        self.n = [0] * rows                         # trailing tokens present so far (in the head, or pushed)
+        self.todo = [deque() for _ in range(rows)]  # (pos, id) received, not yet written to the trailing buffer
+        self.closed = [True] * rows                 # no more text comes: the end-of-text position is accounted for
+
+    def reset(self, b: int, n0: int, closed: bool):
+        """Row b starts a request whose prompt holds n0 trailing tokens (closed: and its whole text)."""
+        self.n[b], self.closed[b] = int(n0), bool(closed)
+        self.todo[b].clear()
+
+    def push(self, b: int, ids, vocab: int, who=None):
+        """Row b received ids.  Positions at or past the cap are counted and dropped.  An id outside [0, vocab) raises
+        ValueError: the ids before it stay accepted, it and the ones after it are not."""
+        for t in ids:
+            if not 0 <= t < vocab:  # the gather would read outside the embedding table
+                raise ValueError(f"text id {t} pushed for {who or f'row {b}'} is outside the text vocabulary ({vocab})")
+            if self.n[b] < self.cap:
+                self.todo[b].append((self.n[b], t))
+            self.n[b] += 1
+
+    def close(self, b: int, eos_id: int):
+        """Row b's text is over: the end-of-text id takes the next position.  A second close changes nothing."""
+        if self.closed[b]:
+            return
+        if self.n[b] < self.cap:
+            self.todo[b].append((self.n[b], int(eos_id)))
+        self.closed[b] = True
+
+    def due(self, frame_of, rows):
+        """The (row, pos, id) items to hand to append_text before the next replay, in which row b is at frame
+        frame_of(b): none unless some row of `rows` has its next unwritten position fewer than LOW frames ahead; then
+        every row of `rows` up to AHEAD frames ahead."""
+        if not any(self.todo[b] and self.todo[b][0][0] < frame_of(b) + self.LOW for b in rows):
+            return []
+        items = []
+        for b in rows:
+            q, end = self.todo[b], frame_of(b) + self.AHEAD
+            while q and q[0][0] < end:
+                items.append((b,) + q.popleft())
+        return items
+
+
+class TextGate:
+    """A streamed request's trailing text between its feed and its session: drains the feed into a
+    TextAccount, queues the appends that are due, and says which frame replays may be queued.  Used by the thread that
+    runs the generator only; other threads touch the feed."""
+
     def __init__(self, feed, n0, eos_id: int):
         self.feed, self.eos_id = feed, int(eos_id)
-        self.n = [int(x) for x in n0]          # trailing tokens present so far (in the head, or pushed)
-        self.todo = [deque() for _ in self.n]  # (pos, id) received, not yet written to the trailing buffer
-        self.closed = [False] * len(self.n)    # the row's end-of-text position is written
+        self.acct = TextAccount(len(n0), 0)    # (the cap comes with bind)
+        for b, x in enumerate(n0):
+            self.acct.reset(b, x, False)
+        self.n, self.closed = self.acct.n, self.acct.closed
         self.finished = [False] * len(self.n)  # the row is known to have reached its end-of-speech token
         self.eng = self.s = None
 
     def bind(self, eng, s, max_frames: int, use_graph: bool):
-        self.eng, self.s, self.cap, self.use_graph = eng, s, int(max_frames), use_graph
+        self.eng, self.s, self.acct.cap, self.use_graph = eng, s, int(max_frames), use_graph
 
     def poll(self, f: int = 0):
         """Drain the feed without blocking; queue the projections of the tokens that replay f and the next ones read
@@ -529,21 +582,11 @@ class TextGate:
         pieces, closed = self.feed.drain()
         vocab = self.eng.text_emb.shape[0]
         for b, ids in enumerate(pieces):
-            for t in ids:
-                if not 0 <= t < vocab:  # the gather would read outside the embedding table
-                    raise ValueError(f"text id {t} pushed for row {b} is outside the text vocabulary ({vocab})")
-                if self.n[b] < self.cap:
-                    self.todo[b].append((self.n[b], t))
-                self.n[b] += 1
+            self.acct.push(b, ids, vocab)
         for b in closed:
-            if self.n[b] < self.cap:
-                self.todo[b].append((self.n[b], self.eos_id))
-            self.closed[b] = True
-        if any(q and q[0][0] < f + self.LOW for q in self.todo):
-            items = []
-            for b, q in enumerate(self.todo):
-                while q and q[0][0] < f + self.AHEAD:
-                    items.append((b,) + q.popleft())
+            self.acct.close(b, self.eos_id)
+        items = self.acct.due(lambda b: f, range(len(self.n)))
+        if items:
             self.eng.append_text(self.s, items, self.use_graph)
 
     def row_ready(self, b: int, f: int) -> bool:
@@ -620,7 +663,6 @@ class LiveSlots(SlotTable):
         self.n, self.B, self.max_frames = 0, int(slots), int(max_frames)
         self.lens, self.cap = {}, {}                    # request -> prompt length, frame cap
         self.P = 0
-        self.queue = deque()                            # (unused: the loop keeps the waiting requests themselves)
         self.req = [-1] * self.B
         self.start = [0] * self.B
         self.slot_p = [0] * self.B
@@ -651,6 +693,141 @@ class LiveSlots(SlotTable):
         self.cap.pop(i, None)
         self.start[b], self.req[b] = self.frame, -1
         return -1
+
+
+@dataclass
+class LiveRow:
+    """What a live serving run knows about one batch row beyond the slot table and the text account."""
+    seen: int = 0            # frames of the row's request already reported
+    fresh: bool = True       # the row's request has not been reported yet
+    cp_ran: bool = False     # the row was held in the last replay: its current frame's codes are complete
+    starved: object = None   # host time since which the row has been held
+    kill: object = None      # why the row's request is to be retired: "cancel", "timeout", an exception
+    opened: bool = False     # the row's request gets its text while it decodes
+    primed: bool = False     # the row has been prefilled at least once
+
+    def reset(self):
+        """The row's request starts or is over: everything but `primed` as in a new record."""
+        self.__init__(primed=self.primed)
+
+
+class _LiveRun:
+    """The host state of one serve_live_iter run, and the steps between two replays that change it."""
+
+    def __init__(self, eng: "TalkerEngine", s: Session, queue, prepare, seed: int, max_prompt: int, text_eos: int):
+        self.eng, self.s, self.queue, self.prepare, self.seed = eng, s, queue, prepare, seed
+        self.max_prompt, self.text_eos = int(max_prompt), int(text_eos)
+        self.tab = LiveSlots(s.B, s.max_frames)
+        self.text = TextAccount(s.B, s.max_frames)
+        self.rows = [LiveRow() for _ in range(s.B)]
+        self.waiting = deque()   # requests received, not in a row yet
+        self.early = {}          # open-text request not in a row yet -> [ids pushed so far, text closed]
+        self.where = {}          # request -> its row
+        self.stats = {"frames": 0, "slots": s.B, "requests": 0, "held": 0, "admitted": 0, "retired": 0}
+
+    def feed(self, b: int, ids, close: bool):
+        """Text for row b's request; a bad id marks the request for retirement and drops the rest of the call."""
+        try:
+            self.text.push(b, ids, self.eng.text_emb.shape[0], f"request {self.tab.req[b]}")
+        except ValueError as e:
+            self.rows[b].kill = self.rows[b].kill or e
+            return
+        if close:
+            self.text.close(b, self.text_eos)
+
+    def drain(self):
+        """Take in what the queue received: new requests wait, text goes to its row or is kept until the request has
+        one, a cancel marks a decoding request and drops a waiting one.  Returns (the dropped ones, queue closed)."""
+        new, pushed, text_closed, cancelled, q_closed = self.queue.drain()
+        for r in new:
+            self.waiting.append(r)
+            if r.open_text:
+                self.early[r.id] = [[], False]
+        for i, ids in pushed.items():
+            if i in self.where:
+                self.feed(self.where[i], ids, False)
+            elif i in self.early:
+                self.early[i][0].extend(ids)
+        for i in text_closed:
+            if i in self.where:
+                self.feed(self.where[i], [], True)
+            elif i in self.early:
+                self.early[i][1] = True
+        notes = []
+        for i in cancelled:
+            if i in self.where:
+                row = self.rows[self.where[i]]
+                row.kill = row.kill or "cancel"
+                continue
+            for r in [r for r in self.waiting if r.id == i]:
+                self.waiting.remove(r)
+                self.early.pop(i, None)
+                self.queue.over(i)
+                self.stats["requests"] += 1
+                notes.append(i)
+        return notes, q_closed
+
+    def admit(self, notes: list):
+        """Waiting requests take the idle rows, first in first out; one that is refused is added to `notes`."""
+        eng, s, tab, max_prompt = self.eng, self.s, self.tab, self.max_prompt
+        for b in range(tab.B):
+            while tab.req[b] < 0 and self.waiting:
+                r = self.waiting.popleft()
+                self.stats["requests"] += 1
+                try:
+                    emb, trail, rgp, plan = self.prepare(r)
+                    P = int(emb.shape[0])
+                    if P > max_prompt:
+                        raise ValueError(f"prompt of {P} positions exceeds max_prompt ({max_prompt})")
+                    records = rgp.row_records(0, self.seed)
+                except Exception as e:  # noqa: BLE001 -- the request is refused, the loop goes on
+                    self.early.pop(r.id, None)
+                    self.queue.over(r.id, rejected=e)
+                    notes.append(r.id)
+                    continue
+                eng.serve_queued[r.id] = time.perf_counter()
+                eng._prefill_slot(s, b, (emb, trail), r.id, records, prefix=plan)
+                tab.admit(b, r.id, P, r.frame_cap)
+                self.where[r.id], row = b, self.rows[b]
+                row.reset()
+                row.primed, row.opened = True, r.open_text
+                self.text.reset(b, max(len(r.input_ids) - 4, 0) if r.open_text else 0, not r.open_text)
+                if r.open_text:
+                    self.feed(b, *self.early.pop(r.id))
+                self.stats["admitted"] += 1
+
+    def lacks_text(self, b: int) -> bool:
+        """Busy row b is to be held out of the next replay: the text token that replay reads has not come."""
+        row, tab = self.rows[b], self.tab
+        return (row.opened and not self.text.closed[b] and row.kill is None and not tab.capped(b)
+                and self.text.n[b] <= tab.frames(b))
+
+    def hold(self, busy, now: float):
+        """The rows of `busy` to hold out of the next replay; one starved for queue.timeout is marked for retirement."""
+        held = []
+        for b in busy:
+            row = self.rows[b]
+            if self.lacks_text(b):
+                held.append(b)
+                if row.starved is None:
+                    row.starved = now
+                if row.cp_ran and now - row.starved >= self.queue.timeout:
+                    row.kill = "timeout"
+            else:
+                row.starved = None
+        return held
+
+    def retire(self, b: int, natural: bool):
+        """Row b's request is over (natural: by its EOS or frame cap): the row goes idle until a request takes it."""
+        i, kill = self.tab.req[b], self.rows[b].kill
+        self.queue.over(i, timed_out=kill == "timeout" and not natural,
+                        rejected=kill if isinstance(kill, BaseException) and not natural else None)
+        del self.where[i]
+        self.tab.retire(b)
+        self.s.idle(b)
+        self.stats["retired"] += 1
+        self.rows[b].reset()
+        self.text.reset(b, 0, True)
 
 
 class TalkerEngine:
@@ -1278,7 +1455,7 @@ class TalkerEngine:
                 self._prefill_slot(s, b, requests[i], pids[i], gp.row_records(i, seed) if gp.per_row else None,
                                    prefix=None if prefix is None else prefix.rows(i, i + 1))
             else:
-                s.finished[b:b + 1].fill_(1)  # idle slot: emits EOS until the session ends
+                s.idle(b)
 
         try:
             with K.use_workspace(s.ws):
@@ -1325,7 +1502,6 @@ class TalkerEngine:
                 return
             s, tab, refill = run
             B = tab.B
-            eos = self.tc["codec_eos_token_id"]
             seen = [0] * B       # frames of the slot's request already reported
             fresh = [True] * B   # the slot's request has not been reported yet
             last_report = 0
@@ -1336,30 +1512,47 @@ class TalkerEngine:
                         or any(fresh[b] and tab.frame - tab.start[b] >= first for b in busy)):
                     continue
                 last_report = tab.frame
-                # frames [0, k_b) of slot b are final and column k_b holds its next cb0 (EOS of an ending request)
-                k = [tab.frames(b) if tab.req[b] >= 0 else 0 for b in range(B)]
-                c0 = torch.empty(B, max(k) + 1, dtype=torch.int32, pin_memory=True)
-                c0.copy_(s.codes[:, :max(k) + 1, 0], non_blocking=True)
-                fw = _flag_word(s)
-                hf = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                if fw is not None:
-                    hf.copy_(fw, non_blocking=True)
-                torch.cuda.current_stream(self.dev).synchronize()
-                if int(hf[0]) != 0:  # session-wide and sticky: every request in flight is suspect
-                    _clear_flags(s)
-                    raise HandoffError({tab.req[b] for b in busy}, tab.queue)
+                got = self._report(s, tab, busy, seen, tab.queue)
                 report = [None] * B
                 for b in busy:
-                    hit = (c0[b, seen[b]:k[b] + 1] == eos).nonzero()
-                    f = seen[b] + int(hit[0]) if hit.numel() else k[b]
-                    ended = bool(hit.numel()) or tab.capped(b)
-                    report[b] = (tab.req[b], seen[b], f, ended, int((c0[b, seen[b]:f] != 0).sum()))
+                    f, hit_eos, nz = got[b]
+                    report[b] = (tab.req[b], seen[b], f, hit_eos or tab.capped(b), nz)
                     seen[b], fresh[b] = f, False
                 yield s, report
                 for b in busy:
                     if report[b][3]:
                         seen[b], fresh[b] = 0, True
                         refill(b)
+
+    def _report(self, s: Session, tab: SlotTable, busy, seen, not_started, cp_ran=()):
+        """The report step of serve_iter and serve_live_iter: one pinned copy of the cb0 columns of the frames issued
+        so far together with the hand-off flag word, and one synchronise of the stream.  A hand-off give-up clears the
+        flags and raises HandoffError (in flight: every busy row's request; `not_started` as given).  Returns per row
+        None, or for a row of `busy` (f, hit_eos, nz): frames [seen[b], f) of its request are final, nz of them with a
+        nonzero cb0, and hit_eos when f is where its EOS stands.  Frames [0, k_b) of row b are final and column k_b
+        holds its next cb0 (EOS of an ending request); for a row of `cp_ran` (held in the last replay, its code
+        predictor ran) frame k_b is final too, and the column behind it is not read."""
+        B, eos = tab.B, self.tc["codec_eos_token_id"]
+        k = [tab.frames(b) if tab.req[b] >= 0 else 0 for b in range(B)]
+        c0 = torch.empty(B, max(k) + 1, dtype=torch.int32, pin_memory=True)
+        c0.copy_(s.codes[:, :max(k) + 1, 0], non_blocking=True)
+        fw = _flag_word(s)
+        hf = torch.zeros(1, dtype=torch.int32, pin_memory=True)
+        if fw is not None:
+            hf.copy_(fw, non_blocking=True)
+        torch.cuda.current_stream(self.dev).synchronize()
+        if int(hf[0]) != 0:  # session-wide and sticky: every request in flight is suspect
+            _clear_flags(s)
+            raise HandoffError({tab.req[b] for b in busy}, not_started)
+        out = [None] * B
+        for b in busy:
+            hit = (c0[b, seen[b]:k[b] + 1] == eos).nonzero()
+            if hit.numel():
+                f = seen[b] + int(hit[0])
+            else:
+                f = k[b] + (1 if b in cp_ran and not tab.capped(b) else 0)
+            out[b] = (f, bool(hit.numel()), int((c0[b, seen[b]:f] != 0).sum()))
+        return out
 
     # ---------------------------------------------------------------- live serving (DESIGN §19)
     def serve_live_iter(self, queue, tts_pad, gp: GenParams, prepare, slots: int = 8, max_prompt: int = 512,
@@ -1390,15 +1583,13 @@ class TalkerEngine:
             raise ValueError(f"serve_live takes 1..64 batch rows, got {slots}")
         if not gp.per_row:
             raise ValueError("serve_live_iter needs per-request sampling parameters (a per-row session)")
-        max_frames = max(gp.max_new_tokens - 1, 1)
-        max_prompt, every, first = int(max_prompt), max(1, int(every)), max(1, int(first))
-        tab = LiveSlots(B, max_frames)
+        every, first = max(1, int(every)), max(1, int(first))
         seed = gp.resolve_seed()
-        eos, H, dev = self.tc["codec_eos_token_id"], self.talker.H, self.dev
-        vocab = self.text_emb.shape[0]
-        stats = {"frames": 0, "slots": B, "requests": 0, "held": 0, "admitted": 0, "retired": 0}
+        H, dev = self.talker.H, self.dev
         self.serve_queued = {}
-        s = self.session(B, max_prompt, max_frames, gp)
+        s = self.session(B, int(max_prompt), max(gp.max_new_tokens - 1, 1), gp)
+        run = _LiveRun(self, s, queue, prepare, seed, max_prompt, text_eos)
+        tab, rows = run.tab, run.rows
         try:
             with K.use_workspace(s.ws):
                 pad_row = tts_pad.reshape(1, H).float().to(dev)
@@ -1406,184 +1597,67 @@ class TalkerEngine:
                 s.seed.fill_(seed)
                 s.stashed = 0
                 idle_rec = GenParams(do_sample=False, subtalker_dosample=False).row_records(0, seed)
-                waiting = deque()   # requests received, not in a row yet
-                text = {}           # open-text request not in a row yet -> [ids pushed so far, text closed]
-                where = {}          # request -> its row
-                # per row, TextGate's account: trailing tokens present, (pos, id) not written yet, end of text written
-                n, todo, closed, opened = [0] * B, [deque() for _ in range(B)], [True] * B, [False] * B
-                seen = [0] * B          # frames of the row's request already reported
-                fresh = [True] * B      # the row's request has not been reported yet
-                cp_ran = [False] * B    # the row was held in the last replay: its current frame's codes are complete
-                starved = [None] * B    # host time since which the row has been held
-                kill = [None] * B       # why the row's request is to be retired: "cancel", "timeout", an exception
-                primed = [False] * B    # the row has been prefilled at least once
                 last_report, dirty = 0, False
-
-                def feed(b, ids, close):
-                    for t in ids:
-                        if not 0 <= t < vocab:  # the gather would read outside the embedding table
-                            kill[b] = kill[b] or ValueError(f"text id {t} pushed for request {tab.req[b]} is outside "
-                                                            f"the text vocabulary ({vocab})")
-                            return
-                        if n[b] < max_frames:
-                            todo[b].append((n[b], t))
-                        n[b] += 1
-                    if close and not closed[b]:
-                        if n[b] < max_frames:
-                            todo[b].append((n[b], int(text_eos)))
-                        closed[b] = True
-
                 while True:
-                    new, pushed, text_closed, cancelled, q_closed = queue.drain()
-                    for r in new:
-                        waiting.append(r)
-                        if r.open_text:
-                            text[r.id] = [[], False]
-                    for i, ids in pushed.items():
-                        if i in where:
-                            feed(where[i], ids, False)
-                        elif i in text:
-                            text[i][0].extend(ids)
-                    for i in text_closed:
-                        if i in where:
-                            feed(where[i], [], True)
-                        elif i in text:
-                            text[i][1] = True
-                    notes = []  # requests that end without decoding
-                    for i in cancelled:
-                        if i in where:
-                            kill[where[i]] = kill[where[i]] or "cancel"
-                            continue
-                        for r in [r for r in waiting if r.id == i]:
-                            waiting.remove(r)
-                            text.pop(i, None)
-                            queue.over(i)
-                            stats["requests"] += 1
-                            notes.append(i)
-                    for b in range(B):
-                        while tab.req[b] < 0 and waiting:
-                            r = waiting.popleft()
-                            stats["requests"] += 1
-                            try:
-                                emb, trail, rgp, plan = prepare(r)
-                                P = int(emb.shape[0])
-                                if P > max_prompt:
-                                    raise ValueError(f"prompt of {P} positions exceeds max_prompt ({max_prompt})")
-                                records = rgp.row_records(0, seed)
-                            except Exception as e:  # noqa: BLE001 -- the request is refused, the loop goes on
-                                text.pop(r.id, None)
-                                queue.over(r.id, rejected=e)
-                                notes.append(r.id)
-                                continue
-                            self.serve_queued[r.id] = time.perf_counter()
-                            self._prefill_slot(s, b, (emb, trail), r.id, records, prefix=plan)
-                            tab.admit(b, r.id, P, r.frame_cap)
-                            where[r.id], primed[b] = b, True
-                            seen[b], fresh[b], cp_ran[b], starved[b], kill[b] = 0, True, False, None, None
-                            todo[b].clear()
-                            opened[b], closed[b] = r.open_text, not r.open_text
-                            n[b] = max(len(r.input_ids) - 4, 0) if r.open_text else 0
-                            if r.open_text:
-                                feed(b, *text.pop(r.id))
-                            stats["admitted"] += 1
+                    notes, q_closed = run.drain()
+                    run.admit(notes)
                     if notes:
                         yield None, notes
-                    for b in range(B):
-                        if not primed[b]:  # an idle row decodes one pad position, finished, until a request takes it
+                    for b, row in enumerate(rows):
+                        if not row.primed:  # an idle row decodes one pad position, finished, until a request takes it
                             self._prefill_slot(s, b, (pad_row, pad_row), 0, idle_rec)
-                            s.finished[b:b + 1].fill_(1)
-                            primed[b] = True
+                            s.idle(b)
+                            row.primed = True
                     busy = tab.busy()
                     if not busy:
-                        if waiting:
+                        if run.waiting:
                             continue
                         if q_closed:
                             break
                         queue.wait(1.0)
                         continue
-                    # text a little ahead of the frames, as TextGate.poll writes it
-                    if any(todo[b] and todo[b][0][0] < tab.frames(b) + TextGate.LOW for b in busy):
-                        items = []
-                        for b in busy:
-                            while todo[b] and todo[b][0][0] < tab.frames(b) + TextGate.AHEAD:
-                                items.append((b,) + todo[b].popleft())
+                    items = run.text.due(tab.frames, busy)  # text a little ahead of the frames
+                    if items:
                         self.append_text(s, items, use_graph)
                     now = time.perf_counter()
-                    held = []
-                    for b in busy:
-                        if (opened[b] and not closed[b] and kill[b] is None and not tab.capped(b)
-                                and n[b] <= tab.frames(b)):
-                            held.append(b)
-                            if starved[b] is None:
-                                starved[b] = now
-                            if cp_ran[b] and now - starved[b] >= queue.timeout:
-                                kill[b] = "timeout"
-                        else:
-                            starved[b] = None
-                    force = any(kill[b] is not None for b in busy)
-                    if not force and (len(held) < len(busy) or any(not cp_ran[b] for b in held)):
-                        mask = sum(1 << b for b in held)
-                        self._run_frame_held(s, min(tab.keys(), s.Lmax), mask, use_graph)
+                    held = run.hold(busy, now)
+                    force = any(rows[b].kill is not None for b in busy)
+                    if not force and (len(held) < len(busy) or any(not rows[b].cp_ran for b in held)):
+                        self._run_frame_held(s, min(tab.keys(), s.Lmax), sum(1 << b for b in held), use_graph)
                         for b in busy:
-                            cp_ran[b] = b in held
-                            if cp_ran[b]:
+                            rows[b].cp_ran = b in held
+                            if rows[b].cp_ran:
                                 tab.hold(b)
                         tab.frame += 1
-                        stats["held"] += len(held)
+                        run.stats["held"] += len(held)
                         dirty = True
                         # (serve_iter's schedule: the codec then sees the feeds serve_stream gives it)
                         if not (tab.frame - last_report >= every
-                                or any(fresh[b] and tab.frames(b) + cp_ran[b] >= first for b in busy)):
+                                or any(rows[b].fresh and tab.frames(b) + rows[b].cp_ran >= first for b in busy)):
                             continue
                     elif not (dirty or force):
                         # nothing can run and nothing is new: wait for text, a request or a cancel, at most until the
                         # first starved row's time is up
-                        left = min(starved[b] + queue.timeout - now for b in held)
+                        left = min(rows[b].starved + queue.timeout - now for b in held)
                         queue.wait(min(max(left, 0.0), 1.0))
                         continue
                     last_report, dirty = tab.frame, False
-                    # frames [0, k_b) of row b are final and column k_b holds its next cb0 (EOS of an ending request);
-                    # a held row's frame k_b is final too, and the column behind it is not read
-                    k = [tab.frames(b) if tab.req[b] >= 0 else 0 for b in range(B)]
-                    c0 = torch.empty(B, max(k) + 1, dtype=torch.int32, pin_memory=True)
-                    c0.copy_(s.codes[:, :max(k) + 1, 0], non_blocking=True)
-                    fw = _flag_word(s)
-                    hf = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-                    if fw is not None:
-                        hf.copy_(fw, non_blocking=True)
-                    torch.cuda.current_stream(self.dev).synchronize()
-                    if int(hf[0]) != 0:  # session-wide and sticky: every request in flight is suspect
-                        _clear_flags(s)
-                        raise HandoffError({tab.req[b] for b in busy}, [r.id for r in waiting])
+                    got = self._report(s, tab, busy, [row.seen for row in rows], [r.id for r in run.waiting],
+                                       [b for b in busy if rows[b].cp_ran])
                     report, natural = [None] * B, [False] * B
                     for b in busy:
-                        hit = (c0[b, seen[b]:k[b] + 1] == eos).nonzero()
-                        natural[b] = bool(hit.numel()) or tab.capped(b)
-                        if hit.numel():
-                            f = seen[b] + int(hit[0])
-                        else:
-                            f = k[b] + (1 if cp_ran[b] and not tab.capped(b) else 0)
-                        ended = natural[b] or kill[b] is not None
-                        report[b] = (tab.req[b], seen[b], f, ended, int((c0[b, seen[b]:f] != 0).sum()))
-                        seen[b], fresh[b] = f, False
+                        f, hit_eos, nz = got[b]
+                        natural[b] = hit_eos or tab.capped(b)
+                        report[b] = (tab.req[b], rows[b].seen, f, natural[b] or rows[b].kill is not None, nz)
+                        rows[b].seen, rows[b].fresh = f, False
                     yield s, report
                     for b in busy:
-                        if not report[b][3]:
-                            continue
-                        i = tab.req[b]
-                        queue.over(i, timed_out=kill[b] == "timeout" and not natural[b],
-                                   rejected=kill[b] if isinstance(kill[b], BaseException) and not natural[b] else None)
-                        del where[i]
-                        tab.retire(b)
-                        s.finished[b:b + 1].fill_(1)  # idle row: emits EOS until a request takes it
-                        stats["retired"] += 1
-                        todo[b].clear()
-                        opened[b], closed[b], kill[b], starved[b], cp_ran[b] = False, True, None, None, False
-                        seen[b], fresh[b] = 0, True
+                        if report[b][3]:
+                            run.retire(b, natural[b])
                 check_handoffs([s])
         finally:
-            stats["frames"] = tab.frame
-            self.serve_stats = stats
+            run.stats["frames"] = tab.frame
+            self.serve_stats = run.stats
             self.release([s])
 
     def _prefill_slot(self, s: Session, b: int, req, i: int, records=None, prefix=None):
