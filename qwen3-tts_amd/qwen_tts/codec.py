@@ -110,6 +110,8 @@ class CodecDecoder:
                                      wdt)
         self.total_upsample = int(math.prod(d["upsample_rates"]) * math.prod(d["upsampling_ratios"]))
         self._slots = {}  # (B, max_frames) -> [_StreamSlot]: incremental-decode state reused across streams
+        self._row_slots = {}  # (B, max_frames, n_max) -> [_RowStreamSlot]
+        self._old_rope = []  # grown-out (cos, sin): captured feed graphs still read them
         torch.cuda.synchronize()
 
     # ------------------------------------------------------------------------------------------------
@@ -117,9 +119,11 @@ class CodecDecoder:
         K.gemm(x, Wt, out, B * t_out, cin, Wt.N, conv=(t_in, t_out, t_off, getattr(Wt, "dil", 1)), epi=epi, act=act,
                snake=snake)
 
-    def _causal(self, x, Wt, B, T, out, cin, epi=_hip.EPI_STORE, snake=None):
-        dil = getattr(Wt, "dil", 1)
-        self._conv(x, Wt, B, T, T, -(Wt.taps - 1) * dil, out, cin, epi, snake=snake)
+    def _ensure_rope(self, npos):
+        """RoPE tables of at least npos positions.  The outgoing tables stay alive: captured feed graphs read them."""
+        if self.cos.shape[0] < npos:
+            self._old_rope.append((self.cos, self.sin))
+            self.cos, self.sin = K.rope_tables(self.hd, self.d["rope_theta"], npos + 64, self.dev)
 
     def _fuses(self, un, x, bb, B, L, C) -> bool:
         """Does forward() run this residual unit as one qt_codec_resunit launch: the kernel has the shape, the decoder
@@ -139,97 +143,89 @@ class CodecDecoder:
             self._unit_fused[key] = hit
         return hit
 
-    def _transformer(self, h, B, T):
-        """C3 (K:500-574).  h: [B*T][lat] (adt) -> [B*T][lat] (adt)."""
-        dev, R = self.dev, B * T
-        hid, nh, nkv, D = self.hid, self.heads, self.kvh, self.hd
+    def _transformer(self, st, h, n):
+        """C3 (K:500-574).  h: [B*n][lat] (adt) -> [B*n][lat] (adt); positions, key counts and K/V caches are st's."""
+        dev, R = self.dev, st.B * n
+        hid, nh, nkv, D, inter = self.hid, self.heads, self.kvh, self.hd, self.d["intermediate_size"]
         x = torch.empty(R, self.inp.N, dtype=torch.float32, device=dev)
         K.gemm(h, self.inp, x, R, self.lat, self.inp.N)
-        if self.cos.shape[0] < T:
-            self.cos, self.sin = K.rope_tables(D, self.d["rope_theta"], T + 64, dev)
-        pos = torch.arange(T, device=dev, dtype=torch.int32).repeat(B)
-        meta_b = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(T)
-        row_len = pos + 1
+        pos, meta_b, row_len, caches, Lmax, max_keys = st.bind(n)
         row_start = torch.zeros_like(pos)
         qkv_w = (nh + 2 * nkv) * D
         qkv = torch.empty(R, qkv_w, dtype=torch.float32, device=dev)
         q = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
         att = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
-        hmid = torch.empty(R, self.d["intermediate_size"], dtype=torch.float32, device=dev)
-        kc = torch.empty(B, nkv, T, D, dtype=torch.float32, device=dev)
-        vc = torch.empty_like(kc)
+        hmid = torch.empty(R, inter, dtype=torch.float32, device=dev)
         eps, win = self.d["rms_norm_eps"], self.d["sliding_window"]
-        for L in self.layers:
+        for L, (kc, vc) in zip(self.layers, caches):
             K.gemm(x, L["qkv"], qkv, R, hid, qkv_w, rms=True, eps=eps)
-            K.qkv_post(qkv, R, nh, nkv, D, None, None, eps, self.cos, self.sin, pos, meta_b, pos, q, kc, vc, T)
-            K.attention(q, R, nh, nkv, D, kc, vc, T, meta_b, row_start, row_len, att, min(win, T), window=win)
+            K.qkv_post(qkv, R, nh, nkv, D, None, None, eps, self.cos, self.sin, pos, meta_b, pos, q, kc, vc, Lmax)
+            K.attention(q, R, nh, nkv, D, kc, vc, Lmax, meta_b, row_start, row_len, att, max_keys, window=win)
             K.gemm(att, L["o"], x, R, nh * D, hid, colscale=L["ls1"], epi=_hip.EPI_ADD)
-            K.gemm(x, L["gu"], hmid, R, hid, self.d["intermediate_size"], rms=True, eps=eps, epi=_hip.EPI_SWIGLU)
-            K.gemm(hmid, L["down"], x, R, self.d["intermediate_size"], hid, colscale=L["ls2"], epi=_hip.EPI_ADD)
+            K.gemm(x, L["gu"], hmid, R, hid, inter, rms=True, eps=eps, epi=_hip.EPI_SWIGLU)
+            K.gemm(hmid, L["down"], x, R, inter, hid, colscale=L["ls2"], epi=_hip.EPI_ADD)
         y = torch.empty(R, self.lat, dtype=self.adt, device=dev)
         K.gemm(x, self.outp, y, R, hid, self.lat, rms=True, eps=eps)
         return y
 
-    def forward(self, codes: torch.Tensor) -> torch.Tensor:
-        """codes int [B, T, 16] (device) -> pcm fp32 [B, 1920T-555] (K:868-883)."""
-        B, T, Qn = codes.shape
-        dev, adt = self.dev, self.adt
-        codes = codes.to(dev, torch.int32).contiguous()
+    def _walk(self, st, codes: torch.Tensor, n: int):
+        """The decoder network, C1-C7, for st.B rows of n frames: codes int32 [B, n, 16] (device) -> clamped PCM
+        [B][rows].  forward(), CodecStream and RowCodecStream all decode through this; st (a _Stage) answers what
+        differs between them: how a stage's input window is formed, where the transformer's positions and caches come
+        from, the decoder blocks' two-tap transposed conv, and whether a residual unit may be one launch.  Graph-
+        capturable when st is: no host-side state, shapes fixed by (B, n) and the stage."""
+        B, dev, adt = st.B, self.dev, self.adt
         # C1
-        o1 = torch.empty(B * T, self.cb_dim, dtype=torch.float32, device=dev)
+        o1 = torch.empty(B * n, self.cb_dim, dtype=torch.float32, device=dev)
         o2 = torch.empty_like(o1)
-        K.rvq_gather(self.tables, Qn, 1, self.tables.shape[1], self.cb_dim, codes, B, T, o1, o2)
+        K.rvq_gather(self.tables, codes.shape[2], 1, self.tables.shape[1], self.cb_dim, codes, B, n, o1, o2)
         cd = self.proj_first.N
-        h = torch.empty(B * T, cd, dtype=adt, device=dev)
-        K.gemm(o1, self.proj_first, h, B * T, self.cb_dim, cd)
-        K.gemm(o2, self.proj_rest, h, B * T, self.cb_dim, cd, epi=_hip.EPI_ADD)
-        # C2
-        x = torch.empty(B * T, self.pre_conv.N, dtype=adt, device=dev)
-        self._causal(h, self.pre_conv, B, T, x, cd)
-        # C3
-        x = self._transformer(x, B, T)
-        # C4
-        L = T
-        C = self.lat
-        for u in self.ups:
+        h = torch.empty(B * n, cd, dtype=adt, device=dev)
+        K.gemm(o1, self.proj_first, h, B * n, self.cb_dim, cd)
+        K.gemm(o2, self.proj_rest, h, B * n, self.cb_dim, cd, epi=_hip.EPI_ADD)
+        # C2, C3
+        x = st.causal("pre", h, n, self.pre_conv, cd)
+        x = self._transformer(st, x, n)
+        st.after_c3(n)
+        # C4: upsample (1-tap transposed conv, no state) + ConvNeXt (causal depthwise k=7 + LayerNorm, then per row)
+        L, C = n, self.lat
+        for i, u in enumerate(self.ups):
             f = u["f"]
             y = torch.empty(B * L * f, C, dtype=adt, device=dev)
             self._conv(x, u["tconv"], B, L, L, 0, y, C)
             L *= f
-            z = torch.empty_like(y)
-            K.dwconv_ln(y, B, L, C, u["dw_w"], u["dw_b"], u["ln_w"], u["ln_b"], 1e-6, z)
+            yin, Hd = st.dw_window(f"dw{i}", y, L, C, u["dw_w"].shape[1] - 1)
+            z = torch.empty_like(yin)
+            K.dwconv_ln(yin, B, Hd + L, C, u["dw_w"], u["dw_b"], u["ln_w"], u["ln_b"], 1e-6, z)
+            if Hd:
+                z = z[:, Hd:].contiguous()
             hmid = torch.empty(B * L, u["pw1"].N, dtype=adt, device=dev)
             K.gemm(z, u["pw1"], hmid, B * L, C, u["pw1"].N, act=_hip.ACT_GELU)
             K.gemm(hmid, u["pw2"], y, B * L, u["pw1"].N, C, colscale=u["gamma"], epi=_hip.EPI_ADD)
             x = y
         # C5
-        ds = self.d["decoder_dim"]
-        y = torch.empty(B * L, self.conv0.N, dtype=adt, device=dev)
-        self._causal(x, self.conv0, B, L, y, C)
-        x, C = y, ds
+        x = st.causal("conv0", x, L, self.conv0, C)
+        C = self.d["decoder_dim"]
         # C6
         # every SnakeBeta feeds a conv: applied to the conv's A operand as it is staged (no separate pass)
-        for blk in self.blocks:
-            r, cout = blk["r"], blk["cout"]
-            Lo = (L - 1) * r
-            y = torch.empty(B * Lo, cout, dtype=adt, device=dev)
-            self._conv(x, blk["tconv"], B, L, L - 1, 0, y, C, snake=blk["s"])
-            L, C, x = Lo, cout, y
-            bb = torch.empty_like(x)
-            for un in blk["units"]:
-                if self._fuses(un, x, bb, B, L, C):
-                    # x_out is a second buffer (tiles read their neighbours' x rows): x and bb swap roles per unit
-                    K.codec_resunit(x, bb, B, L, C, un["c1"], un["s1"], un["c2"], un["s2"])
-                    x, bb = bb, x
-                    continue
-                self._causal(x, un["c1"], B, L, bb, C, snake=un["s1"])
-                self._causal(bb, un["c2"], B, L, x, C, epi=_hip.EPI_ADD, snake=un["s2"])
+        for bi, blk in enumerate(self.blocks):
+            rows, x = st.tconv2(bi, x, L, C, blk)
+            L, C = rows * blk["r"], blk["cout"]
+            if L == 0:  # (a stream's first feed of too few rows)
+                return torch.zeros(B, 0, dtype=torch.float32, device=dev)
+            for ui, un in enumerate(blk["units"]):
+                x = st.unit(bi, ui, un, x, L, C)
         # C7
-        out = torch.empty(B * L, self.conv_last.N, dtype=torch.float32, device=dev)
-        self._conv(x, self.conv_last, B, L, L, -(self.conv_last.taps - 1), out, C, snake=self.s_last)
+        out = st.causal("last", x, L, self.conv_last, C, len(self.blocks), snake=self.s_last,
+                        out=torch.empty(B * L, self.conv_last.N, dtype=torch.float32, device=dev))
         pcm = out[:, 0].contiguous()
         K.clamp_pcm(pcm, pcm.numel(), pcm)
         return pcm.view(B, L)
+
+    def forward(self, codes: torch.Tensor) -> torch.Tensor:
+        """codes int [B, T, 16] (device) -> pcm fp32 [B, 1920T-555] (K:868-883)."""
+        B, T, _ = codes.shape
+        return self._walk(_OneShot(self, B), codes.to(self.dev, torch.int32).contiguous(), T)
 
     def stream(self, B: int, max_frames: int) -> "CodecStream":
         """A stateful incremental decode of up to max_frames frames (one reference chunk with its context); close() it
@@ -248,16 +244,16 @@ class CodecDecoder:
                 int(d["decoder_dim"]), tuple(int(r) for r in d["upsample_rates"]),
                 tuple(int(r) for r in d["upsampling_ratios"]))
 
-    def _acquire_slot(self, B, max_frames) -> "_StreamSlot":
-        pool = self._slots.setdefault((B, max_frames), [])
-        for sl in pool:
-            if not sl.busy:
-                sl.reset()
-                sl.busy = True
-                return sl
-        sl = _StreamSlot(self, B, max_frames)
+    def _acquire_slot(self, pools, key, make):
+        """A free state slot of pools[key] (self._slots or self._row_slots), reset, or a new one from make()."""
+        pool = pools.setdefault(key, [])
+        sl = next((s for s in pool if not s.busy), None)
+        if sl is None:
+            sl = make()
+            pool.append(sl)
+        else:
+            sl.reset()
         sl.busy = True
-        pool.append(sl)
         return sl
 
     def chunked_decode(self, codes: torch.Tensor, chunk_size=300, left_context_size=25) -> torch.Tensor:
@@ -285,18 +281,161 @@ class CodecDecoder:
         return [a[:int(l)] for a, l in zip(wav, lengths)]
 
 
+class _Stage:
+    """What CodecDecoder._walk asks of a decode mode.  causal(key, x, L, Wt, cin, k, out, epi, snake): a causal conv
+    of L new rows, its input window formed the mode's way (k = decoder blocks passed so far); dw_window: the input of
+    C4's depthwise conv and its leading history rows; tconv2: a decoder block's two-tap transposed conv, returning
+    (rows out, output); bind(n): the transformer's positions, row_batch, key counts, per-layer (K, V) caches, cache
+    length and max_keys; unit: one residual unit."""
+
+    def __init__(self, dec: "CodecDecoder", B: int, slot=None):
+        self.dec, self.B, self.slot = dec, B, slot
+
+    def _out(self, rows, Wt):
+        return torch.empty(self.B * rows, Wt.N, dtype=self.dec.adt, device=self.dec.dev)
+
+    def unit(self, bi, ui, un, x, L, C, bb=None):
+        bb = self.causal(f"u{bi}.{ui}", x, L, un["c1"], C, bi + 1, out=bb, snake=un["s1"])
+        return self.causal(f"v{bi}.{ui}", bb, L, un["c2"], C, bi + 1, out=x, epi=_hip.EPI_ADD, snake=un["s2"])
+
+    def after_c3(self, n):
+        pass
+
+
+class _OneShot(_Stage):
+    """forward(): the whole sequence at once, so a window's history is implicit zero padding (t_off < 0)."""
+
+    def causal(self, key, x, L, Wt, cin, k=0, out=None, epi=_hip.EPI_STORE, snake=None):
+        out = self._out(L, Wt) if out is None else out
+        self.dec._conv(x, Wt, self.B, L, L, -(Wt.taps - 1) * getattr(Wt, "dil", 1), out, cin, epi, snake=snake)
+        return out
+
+    def dw_window(self, key, y, L, C, H):
+        return y, 0
+
+    def tconv2(self, bi, x, L, C, blk):
+        y = torch.empty(self.B * (L - 1) * blk["r"], blk["cout"], dtype=self.dec.adt, device=self.dec.dev)
+        self.dec._conv(x, blk["tconv"], self.B, L, L - 1, 0, y, C, snake=blk["s"])
+        return L - 1, y
+
+    def bind(self, T):
+        dec, B, dev = self.dec, self.B, self.dec.dev
+        dec._ensure_rope(T)
+        pos = torch.arange(T, device=dev, dtype=torch.int32).repeat(B)
+        meta_b = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(T)
+        kc = torch.empty(B, dec.kvh, T, dec.hd, dtype=torch.float32, device=dev)
+        return pos, meta_b, pos + 1, [(kc, torch.empty_like(kc))] * len(dec.layers), T, min(dec.d["sliding_window"], T)
+
+    def unit(self, bi, ui, un, x, L, C):
+        # x_out is a second buffer (tiles read their neighbours' x rows): x and bb swap roles per fused unit
+        bb = torch.empty_like(x)
+        if self.dec._fuses(un, x, bb, self.B, L, C):
+            K.codec_resunit(x, bb, self.B, L, C, un["c1"], un["s1"], un["c2"], un["s2"])
+            return bb
+        return super().unit(bi, ui, un, x, L, C, bb)
+
+
+class _Streamed(_Stage):
+    """A feed of an incremental decode: every stage's window is [history | x], the history kept on the state slot."""
+
+    def _hist(self, key, H, C, dtype):
+        h = self.slot.hist.get(key)
+        if h is None:  # first use on this slot (eager, never inside a capture): zeros = the one-shot zero padding
+            h = self.slot.hist[key] = torch.zeros(self.B, H, C, dtype=dtype, device=self.dec.dev)
+        return h
+
+    def causal(self, key, x, L, Wt, cin, k=0, out=None, epi=_hip.EPI_STORE, snake=None):
+        """x [B][L][cin] new input rows -> [B][L][Wt.N] outputs of the causal conv (history = previous inputs)."""
+        H = (Wt.taps - 1) * getattr(Wt, "dil", 1)
+        # (a 1-tap conv keeps no state and maps a spurious row to a spurious row: no window)
+        xin = self.window(key, x, L, cin, H, k) if H else x
+        out = self._out(L, Wt) if out is None else out
+        self.dec._conv(xin, Wt, self.B, H + L, L, 0, out, cin, epi=epi, snake=snake)
+        return out
+
+    def dw_window(self, key, y, L, C, H):
+        return self.window(key, y, L, C, H, 0), H
+
+
+class _SlotStage(_Streamed):
+    """One feed of a CodecStream: all rows on the slot's one frame counter; `first` = the decode's first feed."""
+
+    def __init__(self, cs: "CodecStream", first: bool):
+        super().__init__(cs.dec, cs.B, cs.slot)
+        self.first = first
+
+    def window(self, key, x, L, C, H, k):
+        h = self._hist(key, H, C, x.dtype)
+        xin = torch.cat([h, x.view(self.B, L, C)], 1)
+        h.copy_(xin[:, -H:])
+        return xin
+
+    def tconv2(self, bi, x, n, C, blk):
+        """Row t <- inputs t, t + 1: the first feed's n rows give n - 1, a later feed's [last input row | x] gives n."""
+        h = self._hist(f"t{bi}", 1, C, x.dtype)
+        xin = x.view(self.B, n, C) if self.first else torch.cat([h, x.view(self.B, n, C)], 1)
+        xin = xin.contiguous()
+        L = xin.shape[1]
+        h.copy_(xin[:, -1:])
+        out = self._out(L - 1, blk["tconv"])
+        if L > 1:
+            self.dec._conv(xin, blk["tconv"], self.B, L, L - 1, 0, out, C, snake=blk["s"])
+        return L - 1, out
+
+    def bind(self, n):
+        dec, B, sl, dev = self.dec, self.B, self.slot, self.dec.dev
+        # positions nf .. nf + n - 1 from the slot's device frame counter (a captured feed replays with later ones)
+        pos = (torch.arange(n, device=dev, dtype=torch.int32) + sl.nf_dev).repeat(B)
+        meta_b = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(n)
+        return pos, meta_b, pos + 1, zip(sl.kc, sl.vc), sl.Lm, dec.d["sliding_window"]
+
+    def after_c3(self, n):
+        self.slot.nf_dev.add_(n)
+
+
+class _RowStage(_Streamed):
+    """One feed of capacity n of a RowCodecStream: windows, positions and clocks per the slot's row table."""
+
+    def __init__(self, rs: "RowCodecStream", n: int):
+        super().__init__(rs.dec, rs.B, rs.slot)
+        self.heads, self.n = rs.heads, n
+
+    def window(self, key, x, L, C, H, k):
+        """[history | x] of one stage per the row table, the history advanced by each row's own rows; a beginning
+        row's heads[k] spurious rows read as zeros."""
+        h = self._hist(key, H, C, x.dtype)
+        xin = torch.empty(self.B, H + L, C, dtype=x.dtype, device=self.dec.dev)
+        K.stream_window(h, x, xin, self.B, H, L, C, L // self.n, self.heads[k], self.slot.rows)
+        return xin
+
+    def tconv2(self, bi, x, L, C, blk):
+        # always in its continuing form: [last input row | x] -> L rows of r samples
+        xin = self.window(f"t{bi}", x, L, C, 1, bi)
+        y = self._out(L, blk["tconv"])
+        self.dec._conv(xin, blk["tconv"], self.B, L + 1, L, 0, y, C, snake=blk["s"])
+        return L, y
+
+    def bind(self, n):
+        sl = self.slot
+        pos = torch.empty(self.B * n, dtype=torch.int32, device=self.dec.dev)
+        row_len = torch.empty_like(pos)
+        K.stream_rows(sl.nf_dev, sl.rows, self.B, n, pos, row_len)
+        return pos, sl.meta_b[n], row_len, zip(sl.kc, sl.vc), sl.Lm, self.dec.d["sliding_window"]
+
+
 class _StreamSlot:
     """State of one incremental decode, reused by successive CodecStreams of the same (B, max_frames): the K/V caches,
     every stage's input history (updated in place, so captured graphs keep pointing at it), the frame counter as a
     device word, and the feed graphs captured on this slot keyed by (frames per feed, first feed)."""
 
-    def __init__(self, dec: "CodecDecoder", B: int, max_frames: int):
+    def __init__(self, dec: "CodecDecoder", B: int, Lm: int, clocks: int = 1):
         dev = dec.dev
-        self.kc = [torch.zeros(B, dec.kvh, max_frames, dec.hd, dtype=torch.float32, device=dev) for _ in dec.layers]
+        self.Lm = Lm
+        self.kc = [torch.zeros(B, dec.kvh, Lm, dec.hd, dtype=torch.float32, device=dev) for _ in dec.layers]
         self.vc = [torch.zeros_like(k) for k in self.kc]
-        self.nf_dev = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.nf_dev = torch.zeros(clocks, dtype=torch.int32, device=dev)
         self.hist = {}      # stage key -> [B][rows][C]
-        self.graphs = {}    # (n, first) -> (graph, static codes input, static pcm output)
+        self.graphs = {}    # feed key -> (graph, static codes input, static pcm output)
         self.uses = {}
         self.busy = False
         # split-K scratch of this slot's GEMVs: every feed of the slot (eager or captured) uses it, whatever stream
@@ -309,11 +448,72 @@ class _StreamSlot:
         self.nf_dev.zero_()
 
 
+class _RowStreamSlot(_StreamSlot):
+    """State of one per-row incremental decode, pooled per (B, max_frames, n_max): K/V caches of max_frames + n_max
+    positions (a filler row's K/V lands past its row's clock, never on a valid slot), every stage's input history,
+    the per-row frame clocks and the row table (nrow, begin) as static device buffers, the feed graphs keyed by the
+    feed capacity n alone."""
+
+    def __init__(self, dec: "CodecDecoder", B: int, max_frames: int, n_max: int):
+        super().__init__(dec, B, max_frames + n_max, clocks=B)
+        self.rows = torch.zeros(2, B, dtype=torch.int32, device=dec.dev)
+        self.meta_b = {}    # n -> row_batch [B*n]
+        self.table = None   # kernels.CodecRowTable of this slot (export_row / adopt_rows), built on first use
+
+    def reset(self):
+        pass  # (a row restarts from the zero state through its own begin, whatever the slot held)
+
+
 # captured feed graphs (per slot and feed shape, once a shape repeats); QT_CODEC_GRAPH=0 always feeds eagerly (A/B)
 CODEC_GRAPH = _hip.lib_knob("QT_CODEC_GRAPH", 1) != 0
 
 
-class CodecStream:
+class _PooledStream:
+    """What CodecStream and RowCodecStream share: a pooled state slot handed back by close(), and feeds that replay
+    the slot's captured graph of their shape or run eagerly, capturing a shape on its second use."""
+
+    def close(self):
+        if self.slot is not None:
+            self.slot.busy = False
+            self.slot = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _feed(self, key, codes, compute):
+        """compute(codes) -> pcm, the device work of one feed (graph-capturable: no host-side state, shapes fixed by
+        key): replayed if the slot holds a graph for key, else run under the slot's workspace."""
+        slot = self.slot
+        g = slot.graphs.get(key)
+        if g is not None:
+            g[1].copy_(codes)
+            g[0].replay()
+            return g[2]
+        with K.use_workspace(slot.ws):
+            pcm = compute(codes)
+            slot.uses[key] = slot.uses.get(key, 0) + 1
+            if CODEC_GRAPH and slot.uses[key] >= 2:
+                slot.graphs[key] = self._capture(codes, compute)
+        return pcm
+
+    def _capture(self, codes, compute):
+        # capturing executes nothing: the slot state (histories, caches, clocks) is left as the eager feed left it
+        dev = self.dec.dev
+        cin = codes.clone()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(side), K.capturing():
+            with torch.cuda.graph(g, stream=side):
+                out = compute(cin)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        return g, cin, out
+
+
+class CodecStream(_PooledStream):
     """Stateful incremental form of CodecDecoder.forward: frames are fed as they are generated and
     every output sample is computed once.  After n frames have been fed, samples [0, 1920 n - 555) of
     forward(all n frames) are available -- the same prefix, since every stage only looks back (causal convs,
@@ -329,210 +529,32 @@ class CodecStream:
 
     def __init__(self, dec: "CodecDecoder", B: int, max_frames: int):
         self.dec, self.B, self.max_frames = dec, B, max_frames
-        d = dec.d
-        if dec.cos.shape[0] < max_frames:  # old tables stay alive: other slots' captured feed graphs read them
-            dec._old_rope = getattr(dec, "_old_rope", []) + [(dec.cos, dec.sin)]
-            dec.cos, dec.sin = K.rope_tables(dec.hd, d["rope_theta"], max_frames + 64, dec.dev)
-        self.slot = dec._acquire_slot(B, max_frames)
+        dec._ensure_rope(max_frames)
+        self.slot = dec._acquire_slot(dec._slots, (B, max_frames), lambda: _StreamSlot(dec, B, max_frames))
         self.nf = 0  # frames fed
         self.pcm = torch.zeros(B, dec.total_upsample * max_frames, dtype=torch.float32, device=dec.dev)
         self.ns = 0  # valid samples in self.pcm
 
-    def close(self):
-        if self.slot is not None:
-            self.slot.busy = False
-            self.slot = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # -- stages ----------------------------------------------------------------------------------------
-    def _hist(self, key, rows, C, dtype):
-        h = self.slot.hist.get(key)
-        if h is None:  # first use on this slot (eager, never inside a capture): zeros = the one-shot zero padding
-            h = self.slot.hist[key] = torch.zeros(self.B, rows, C, dtype=dtype, device=self.dec.dev)
-        return h
-
-    def _causal(self, key, x, n, Wt, cin, out=None, epi=_hip.EPI_STORE, snake=None):
-        """x [B][n][cin] new input rows -> [B][n][Wt.N] outputs of the causal conv (history = previous inputs)."""
-        dec, B = self.dec, self.B
-        H = (Wt.taps - 1) * getattr(Wt, "dil", 1)
-        if H:
-            h = self._hist(key, H, cin, x.dtype)
-            xin = torch.cat([h, x.view(B, n, cin)], 1)
-            h.copy_(xin[:, -H:])
-        else:
-            xin = x
-        if out is None:
-            out = torch.empty(B * n, Wt.N, dtype=dec.adt, device=dec.dev)
-        dec._conv(xin, Wt, B, H + n, n, 0, out, cin, epi=epi, snake=snake)
-        return out
-
-    def _tconv2(self, key, x, n, Wt, cin, snake, first):
-        """2-tap transposed conv (row t <- inputs t, t + 1): returns (rows out, [B*rows][Wt.N])."""
-        dec, B = self.dec, self.B
-        h = self._hist(key, 1, cin, x.dtype)
-        xin = x.view(B, n, cin) if first else torch.cat([h, x.view(B, n, cin)], 1)
-        xin = xin.contiguous()
-        L = xin.shape[1]
-        h.copy_(xin[:, -1:])
-        rows = L - 1
-        out = torch.empty(B * max(rows, 0), Wt.N, dtype=dec.adt, device=dec.dev)
-        if rows > 0:
-            dec._conv(xin, Wt, B, L, rows, 0, out, cin, snake=snake)
-        return rows, out
-
-    def _transformer(self, h, n):
-        dec, B, dev = self.dec, self.B, self.dec.dev
-        R = B * n
-        hid, nh, nkv, D = dec.hid, dec.heads, dec.kvh, dec.hd
-        x = torch.empty(R, dec.inp.N, dtype=torch.float32, device=dev)
-        K.gemm(h, dec.inp, x, R, dec.lat, dec.inp.N)
-        # positions nf .. nf + n - 1 from the slot's device frame counter (a captured feed replays with later ones)
-        pos = (torch.arange(n, device=dev, dtype=torch.int32) + self.slot.nf_dev).repeat(B)
-        meta_b = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(n)
-        row_len, row_start = pos + 1, torch.zeros_like(pos)
-        qkv_w = (nh + 2 * nkv) * D
-        qkv = torch.empty(R, qkv_w, dtype=torch.float32, device=dev)
-        q = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
-        att = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
-        inter = dec.d["intermediate_size"]
-        hmid = torch.empty(R, inter, dtype=torch.float32, device=dev)
-        eps, win, Lm = dec.d["rms_norm_eps"], dec.d["sliding_window"], self.max_frames
-        for L, kc, vc in zip(dec.layers, self.slot.kc, self.slot.vc):
-            K.gemm(x, L["qkv"], qkv, R, hid, qkv_w, rms=True, eps=eps)
-            K.qkv_post(qkv, R, nh, nkv, D, None, None, eps, dec.cos, dec.sin, pos, meta_b, pos, q, kc, vc, Lm)
-            K.attention(q, R, nh, nkv, D, kc, vc, Lm, meta_b, row_start, row_len, att, win, window=win)
-            K.gemm(att, L["o"], x, R, nh * D, hid, colscale=L["ls1"], epi=_hip.EPI_ADD)
-            K.gemm(x, L["gu"], hmid, R, hid, inter, rms=True, eps=eps, epi=_hip.EPI_SWIGLU)
-            K.gemm(hmid, L["down"], x, R, inter, hid, colscale=L["ls2"], epi=_hip.EPI_ADD)
-        y = torch.empty(R, dec.lat, dtype=dec.adt, device=dev)
-        K.gemm(x, dec.outp, y, R, hid, dec.lat, rms=True, eps=eps)
-        return y
-
-    # -- feeding ---------------------------------------------------------------------------------------
-    def _compute(self, codes: torch.Tensor, n: int, first: bool):
-        """The device work of one feed (graph-capturable: no host-side state, fixed shapes for (n, first)); returns
-        the new clamped PCM rows [B][L]."""
-        dec, B, dev, adt = self.dec, self.B, self.dec.dev, self.dec.adt
-        # C1 (per frame)
-        o1 = torch.empty(B * n, dec.cb_dim, dtype=torch.float32, device=dev)
-        o2 = torch.empty_like(o1)
-        K.rvq_gather(dec.tables, codes.shape[2], 1, dec.tables.shape[1], dec.cb_dim, codes, B, n, o1, o2)
-        cd = dec.proj_first.N
-        h = torch.empty(B * n, cd, dtype=adt, device=dev)
-        K.gemm(o1, dec.proj_first, h, B * n, dec.cb_dim, cd)
-        K.gemm(o2, dec.proj_rest, h, B * n, dec.cb_dim, cd, epi=_hip.EPI_ADD)
-        # C2, C3
-        x = self._causal("pre", h, n, dec.pre_conv, cd)
-        x = self._transformer(x, n)
-        self.slot.nf_dev.add_(n)
-        # C4: upsample (1-tap transposed conv, no state) + ConvNeXt (causal depthwise k=7 + LayerNorm, then per row)
-        L, C = n, dec.lat
-        for i, u in enumerate(dec.ups):
-            f = u["f"]
-            y = torch.empty(B * L * f, C, dtype=adt, device=dev)
-            dec._conv(x, u["tconv"], B, L, L, 0, y, C)
-            L *= f
-            Hd = u["dw_w"].shape[1] - 1
-            hst = self._hist(f"dw{i}", Hd, C, adt)
-            yin = torch.cat([hst, y.view(B, L, C)], 1)
-            hst.copy_(yin[:, -Hd:])
-            z = torch.empty_like(yin)
-            K.dwconv_ln(yin, B, Hd + L, C, u["dw_w"], u["dw_b"], u["ln_w"], u["ln_b"], 1e-6, z)
-            z = z[:, Hd:].contiguous()
-            hmid = torch.empty(B * L, u["pw1"].N, dtype=adt, device=dev)
-            K.gemm(z, u["pw1"], hmid, B * L, C, u["pw1"].N, act=_hip.ACT_GELU)
-            K.gemm(hmid, u["pw2"], y, B * L, u["pw1"].N, C, colscale=u["gamma"], epi=_hip.EPI_ADD)
-            x = y
-        # C5
-        x = self._causal("conv0", x, L, dec.conv0, C)
-        C = dec.d["decoder_dim"]
-        # C6
-        for bi, blk in enumerate(dec.blocks):
-            r, cout = blk["r"], blk["cout"]
-            rows, y = self._tconv2(f"t{bi}", x, L, blk["tconv"], C, blk["s"], first)
-            L, C, x = rows * r, cout, y
-            if L == 0:
-                return torch.zeros(B, 0, dtype=torch.float32, device=dev)
-            for ui, un in enumerate(blk["units"]):
-                bb = self._causal(f"u{bi}.{ui}", x, L, un["c1"], C, snake=un["s1"])
-                self._causal(f"v{bi}.{ui}", bb, L, un["c2"], C, out=x, epi=_hip.EPI_ADD, snake=un["s2"])
-        # C7
-        out = self._causal("last", x, L, dec.conv_last, C, out=torch.empty(B * L, dec.conv_last.N, dtype=torch.float32,
-                                                                            device=dev), snake=dec.s_last)
-        pcm = out[:, 0].contiguous()
-        K.clamp_pcm(pcm, pcm.numel(), pcm)
-        return pcm.view(B, L)
-
     def feed(self, codes: torch.Tensor) -> int:
         """codes int [B, n, 16] (the next n frames) -> number of valid samples now in self.pcm."""
-        dec, B, dev = self.dec, self.B, self.dec.dev
+        dec = self.dec
         n = codes.shape[1]
         if n == 0:
             return self.ns
         if self.nf + n > self.max_frames:
             raise ValueError(f"CodecStream holds {self.max_frames} frames; {self.nf} fed, {n} more given")
-        codes = codes.to(dev, torch.int32).contiguous()
-        key = (n, self.nf == 0)
-        slot = self.slot
-        g = slot.graphs.get(key)
-        if g is not None:
-            g[1].copy_(codes)
-            g[0].replay()
-            pcm = g[2]
-        else:
-            with K.use_workspace(slot.ws):
-                pcm = self._compute(codes, n, key[1])
-                slot.uses[key] = slot.uses.get(key, 0) + 1
-                if CODEC_GRAPH and slot.uses[key] >= 2:
-                    slot.graphs[key] = self._capture(codes, n, key[1])
+        codes = codes.to(dec.dev, torch.int32).contiguous()
+        first = self.nf == 0
+        pcm = self._feed((n, first), codes, lambda c: dec._walk(_SlotStage(self, first), c, n))
         self.nf += n
         L = pcm.shape[1]
         self.pcm[:, self.ns:self.ns + L] = pcm
         self.ns += L
         return self.ns
 
-    def _capture(self, codes, n, first):
-        # capturing executes nothing: the slot state (histories, caches, frame counter) is left as the eager feed left it
-        cin = codes.clone()
-        side = torch.cuda.Stream(device=self.dec.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dec.dev))
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side), K.capturing():
-            with torch.cuda.graph(g, stream=side):
-                out = self._compute(cin, n, first)
-        torch.cuda.current_stream(self.dec.dev).wait_stream(side)
-        return g, cin, out
-
 
 # ---------------------------------------------------------------------------------------------------------------
 # per-row incremental decode: every batch row its own request clock (continuous batching, TTSModel.serve_stream)
-class _RowStreamSlot:
-    """State of one per-row incremental decode, pooled per (B, max_frames, n_max): K/V caches of max_frames + n_max
-    positions (a filler row's K/V lands past its row's clock, never on a valid slot), every stage's input history,
-    the per-row frame clocks and the row table (nrow, begin) as static device buffers, the feed graphs keyed by the
-    feed capacity n alone."""
-
-    def __init__(self, dec: "CodecDecoder", B: int, max_frames: int, n_max: int):
-        dev = dec.dev
-        self.Lm = max_frames + n_max
-        self.kc = [torch.zeros(B, dec.kvh, self.Lm, dec.hd, dtype=torch.float32, device=dev) for _ in dec.layers]
-        self.vc = [torch.zeros_like(k) for k in self.kc]
-        self.nf_dev = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.rows = torch.zeros(2, B, dtype=torch.int32, device=dev)
-        self.meta_b = {}    # n -> row_batch [B*n]
-        self.hist = {}      # stage key -> [B][rows][C]
-        self.graphs = {}    # n -> (graph, static codes input, static pcm output)
-        self.uses = {}
-        self.busy = False
-        self.ws = K.new_workspace(dev)
-        self.table = None   # kernels.CodecRowTable of this slot (export_row / adopt_rows), built on first use
-
-
 @dataclass
 class CodecRowSnapshot:
     """One row's incremental-decode state (RowCodecStream.export_row): the packed block of qt_codec_row_state, the
@@ -543,7 +565,7 @@ class CodecRowSnapshot:
     block: torch.Tensor  # uint8 [nbytes], device
 
 
-class RowCodecStream:
+class RowCodecStream(_PooledStream):
     """CodecStream with a clock per batch row: feed(codes [B, n, 16], nrow [B], begin [B]) -> pcm [B, 1920 n].
 
     Row b consumes its first nrow[b] <= n frames (the rest is filler: computed, never entering any state); with
@@ -559,17 +581,9 @@ class RowCodecStream:
 
     def __init__(self, dec: "CodecDecoder", B: int, max_frames: int, n_max: int = 8):
         self.dec, self.B, self.max_frames, self.n_max = dec, B, max_frames, n_max
-        if dec.cos.shape[0] < max_frames + n_max:  # old tables stay alive: captured feed graphs read them
-            dec._old_rope = getattr(dec, "_old_rope", []) + [(dec.cos, dec.sin)]
-            dec.cos, dec.sin = K.rope_tables(dec.hd, dec.d["rope_theta"], max_frames + n_max + 64, dec.dev)
-        if not hasattr(dec, "_row_slots"):
-            dec._row_slots = {}  # (B, max_frames, n_max) -> [_RowStreamSlot]
-        pool = dec._row_slots.setdefault((B, max_frames, n_max), [])
-        self.slot = next((sl for sl in pool if not sl.busy), None)
-        if self.slot is None:
-            self.slot = _RowStreamSlot(dec, B, max_frames, n_max)
-            pool.append(self.slot)
-        self.slot.busy = True
+        dec._ensure_rope(max_frames + n_max)
+        self.slot = dec._acquire_slot(dec._row_slots, (B, max_frames, n_max),
+                                      lambda: _RowStreamSlot(dec, B, max_frames, n_max))
         self.nf = [0] * B  # frames on each row's clock
         self.live = [False] * B  # the row has begun on this stream (until then the slot's state is another stream's)
         # spurious leading rows of a beginning row after each decoder block
@@ -581,20 +595,9 @@ class RowCodecStream:
             # the feed in which a row begins (nrow >= 1) must cover its spurious rows: later feeds do not mask
             assert self.heads[-1] <= rpf, (self.heads, rpf)
 
-    def close(self):
-        if self.slot is not None:
-            self.slot.busy = False
-            self.slot = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # -- row state in and out (the voice cache) ---------------------------------------------
     def _hist_specs(self):
-        """(stage key, history rows, channels) of every history _compute keeps, in its order."""
+        """(stage key, history rows, channels) of every history a feed keeps, in the walk's order."""
         dec = self.dec
         taps = lambda Wt: (Wt.taps - 1) * getattr(Wt, "dil", 1)  # noqa: E731
         specs = [("pre", taps(dec.pre_conv), dec.proj_first.N)]
@@ -665,103 +668,7 @@ class RowCodecStream:
         for b, sn in pairs:
             self.nf[b], self.live[b] = sn.p, True
 
-    # -- stages ----------------------------------------------------------------------------------------
-    def _window(self, key, x, L, C, H, rpf, head):
-        """[history | x] of one stage per the row table, the history advanced by each row's own rows."""
-        B, dev = self.B, self.dec.dev
-        h = self.slot.hist.get(key)
-        if h is None:  # first use on this slot (eager, never inside a capture)
-            h = self.slot.hist[key] = torch.zeros(B, H, C, dtype=x.dtype, device=dev)
-        xin = torch.empty(B, H + L, C, dtype=x.dtype, device=dev)
-        K.stream_window(h, x, xin, B, H, L, C, rpf, head, self.slot.rows)
-        return xin
-
-    def _causal(self, key, x, L, Wt, cin, rpf, head, out=None, epi=_hip.EPI_STORE, snake=None):
-        dec, B = self.dec, self.B
-        H = (Wt.taps - 1) * getattr(Wt, "dil", 1)
-        # (a 1-tap conv keeps no state and maps a spurious row to a spurious row: no window)
-        xin = self._window(key, x, L, cin, H, rpf, head) if H else x
-        if out is None:
-            out = torch.empty(B * L, Wt.N, dtype=dec.adt, device=dec.dev)
-        dec._conv(xin, Wt, B, H + L, L, 0, out, cin, epi=epi, snake=snake)
-        return out
-
-    def _transformer(self, h, n):
-        dec, B, dev, sl = self.dec, self.B, self.dec.dev, self.slot
-        R = B * n
-        hid, nh, nkv, D = dec.hid, dec.heads, dec.kvh, dec.hd
-        x = torch.empty(R, dec.inp.N, dtype=torch.float32, device=dev)
-        K.gemm(h, dec.inp, x, R, dec.lat, dec.inp.N)
-        pos = torch.empty(R, dtype=torch.int32, device=dev)
-        row_len = torch.empty_like(pos)
-        K.stream_rows(sl.nf_dev, sl.rows, B, n, pos, row_len)
-        meta_b = sl.meta_b[n]
-        row_start = torch.zeros_like(pos)
-        qkv_w = (nh + 2 * nkv) * D
-        qkv = torch.empty(R, qkv_w, dtype=torch.float32, device=dev)
-        q = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
-        att = torch.empty(R, nh * D, dtype=torch.float32, device=dev)
-        inter = dec.d["intermediate_size"]
-        hmid = torch.empty(R, inter, dtype=torch.float32, device=dev)
-        eps, win, Lm = dec.d["rms_norm_eps"], dec.d["sliding_window"], sl.Lm
-        for L, kc, vc in zip(dec.layers, sl.kc, sl.vc):
-            K.gemm(x, L["qkv"], qkv, R, hid, qkv_w, rms=True, eps=eps)
-            K.qkv_post(qkv, R, nh, nkv, D, None, None, eps, dec.cos, dec.sin, pos, meta_b, pos, q, kc, vc, Lm)
-            K.attention(q, R, nh, nkv, D, kc, vc, Lm, meta_b, row_start, row_len, att, win, window=win)
-            K.gemm(att, L["o"], x, R, nh * D, hid, colscale=L["ls1"], epi=_hip.EPI_ADD)
-            K.gemm(x, L["gu"], hmid, R, hid, inter, rms=True, eps=eps, epi=_hip.EPI_SWIGLU)
-            K.gemm(hmid, L["down"], x, R, inter, hid, colscale=L["ls2"], epi=_hip.EPI_ADD)
-        y = torch.empty(R, dec.lat, dtype=dec.adt, device=dev)
-        K.gemm(x, dec.outp, y, R, hid, dec.lat, rms=True, eps=eps)
-        return y
-
-    def _compute(self, codes: torch.Tensor, n: int):
-        """The device work of one feed of capacity n (graph-capturable: row state comes from the slot's row table
-        and clocks); returns the clamped PCM rows [B][1920 n]."""
-        dec, B, dev, adt = self.dec, self.B, self.dec.dev, self.dec.adt
-        o1 = torch.empty(B * n, dec.cb_dim, dtype=torch.float32, device=dev)
-        o2 = torch.empty_like(o1)
-        K.rvq_gather(dec.tables, codes.shape[2], 1, dec.tables.shape[1], dec.cb_dim, codes, B, n, o1, o2)
-        cd = dec.proj_first.N
-        h = torch.empty(B * n, cd, dtype=adt, device=dev)
-        K.gemm(o1, dec.proj_first, h, B * n, dec.cb_dim, cd)
-        K.gemm(o2, dec.proj_rest, h, B * n, dec.cb_dim, cd, epi=_hip.EPI_ADD)
-        x = self._causal("pre", h, n, dec.pre_conv, cd, 1, 0)
-        x = self._transformer(x, n)
-        L, C = n, dec.lat
-        for i, u in enumerate(dec.ups):
-            f = u["f"]
-            y = torch.empty(B * L * f, C, dtype=adt, device=dev)
-            dec._conv(x, u["tconv"], B, L, L, 0, y, C)
-            L *= f
-            Hd = u["dw_w"].shape[1] - 1
-            yin = self._window(f"dw{i}", y, L, C, Hd, L // n, 0)
-            z = torch.empty_like(yin)
-            K.dwconv_ln(yin, B, Hd + L, C, u["dw_w"], u["dw_b"], u["ln_w"], u["ln_b"], 1e-6, z)
-            z = z[:, Hd:].contiguous()
-            hmid = torch.empty(B * L, u["pw1"].N, dtype=adt, device=dev)
-            K.gemm(z, u["pw1"], hmid, B * L, C, u["pw1"].N, act=_hip.ACT_GELU)
-            K.gemm(hmid, u["pw2"], y, B * L, u["pw1"].N, C, colscale=u["gamma"], epi=_hip.EPI_ADD)
-            x = y
-        x = self._causal("conv0", x, L, dec.conv0, C, L // n, 0)
-        C = dec.d["decoder_dim"]
-        for bi, blk in enumerate(dec.blocks):
-            r, cout = blk["r"], blk["cout"]
-            # 2-tap transposed conv, always in its continuing form: [last input row | x] -> L rows of r samples
-            xin = self._window(f"t{bi}", x, L, C, 1, L // n, self.heads[bi])
-            y = torch.empty(B * L, blk["tconv"].N, dtype=adt, device=dev)
-            dec._conv(xin, blk["tconv"], B, L + 1, L, 0, y, C, snake=blk["s"])
-            L, C, x = L * r, cout, y
-            hd = self.heads[bi + 1]
-            for ui, un in enumerate(blk["units"]):
-                bb = self._causal(f"u{bi}.{ui}", x, L, un["c1"], C, L // n, hd, snake=un["s1"])
-                self._causal(f"v{bi}.{ui}", bb, L, un["c2"], C, L // n, hd, out=x, epi=_hip.EPI_ADD, snake=un["s2"])
-        out = self._causal("last", x, L, dec.conv_last, C, L // n, self.heads[-1],
-                           out=torch.empty(B * L, dec.conv_last.N, dtype=torch.float32, device=dev), snake=dec.s_last)
-        pcm = out[:, 0].contiguous()
-        K.clamp_pcm(pcm, pcm.numel(), pcm)
-        return pcm.view(B, L)
-
+    # -- feeding ---------------------------------------------------------------------------------------
     def feed(self, codes: torch.Tensor, nrow, begin) -> torch.Tensor:
         """codes int [B, n, 16]; nrow[b] <= n frames of row b are consumed, after a restart when begin[b].  Returns
         pcm fp32 [B, 1920 n] (valid until the next feed of this capacity); row b's valid samples are
@@ -786,31 +693,9 @@ class RowCodecStream:
         slot.rows.copy_(tab.pin_memory(), non_blocking=True)
         if n not in slot.meta_b:
             slot.meta_b[n] = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(n)
-        g = slot.graphs.get(n)
-        if g is not None:
-            g[1].copy_(codes)
-            g[0].replay()
-            pcm = g[2]
-        else:
-            with K.use_workspace(slot.ws):
-                pcm = self._compute(codes, n)
-                slot.uses[n] = slot.uses.get(n, 0) + 1
-                if CODEC_GRAPH and slot.uses[n] >= 2:
-                    slot.graphs[n] = self._capture(codes, n)
+        pcm = self._feed(n, codes, lambda c: dec._walk(_RowStage(self, n), c, n))
         for b in range(B):
             if begin[b]:  # (the spurious rows are masked in the beginning feed only: a begin without frames is a reset)
                 self.nf[b], self.live[b] = 0, nrow[b] > 0
             self.nf[b] += nrow[b]
         return pcm
-
-    def _capture(self, codes, n):
-        # capturing executes nothing: the slot state is left as the eager feed left it
-        cin = codes.clone()
-        side = torch.cuda.Stream(device=self.dec.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dec.dev))
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(side), K.capturing():
-            with torch.cuda.graph(g, stream=side):
-                out = self._compute(cin, n)
-        torch.cuda.current_stream(self.dec.dev).wait_stream(side)
-        return g, cin, out

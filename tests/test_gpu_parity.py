@@ -1392,6 +1392,45 @@ def test_codec_stream_matches_forward(preset, dtype):
     assert torch.equal(pcms[1], pcms[2])  # captured replay == the eager feed it was captured from
 
 
+def test_codec_forward_rope_growth_keeps_captured_tables():
+    """A forward() of more than 512 frames grows the decoder's RoPE tables; the outgoing tables stay alive in
+    dec._old_rope, because the feed graphs captured before hold their pointers: a stream on the same pooled slot
+    replays them afterwards to the same bits, still within the fp32 bound of forward()."""
+    from oracle import codec_param_specs, load_preset, synth_state_dict
+    from qwen_tts.codec import CodecDecoder
+    dev = _dev()
+    _, ccfg = load_preset("tiny-customvoice")
+    W = {k: torch.from_numpy(v) for k, v in synth_state_dict(codec_param_specs(ccfg)).items()}
+    dec = CodecDecoder(ccfg, W, dtype="fp32", device=str(dev))
+    g = torch.Generator().manual_seed(17)
+    codes = torch.randint(1, dec.tables.shape[1], (1, 520, dec.tables.shape[0]), generator=g).to(dev, torch.int32)
+
+    def run():
+        cs = dec.stream(1, 8)
+        slot = cs.slot
+        for f in (0, 2, 4):
+            ns = cs.feed(codes[:, f:f + 2])
+        pcm = cs.pcm[:, :ns].clone()
+        cs.close()
+        return slot, pcm
+
+    # the first stream feeds eagerly and captures the continuing feed, the second captures the first feed, the third
+    # replays all three
+    for _ in range(3):
+        slot, before = run()
+    assert sorted(slot.graphs) == [(2, False), (2, True)]
+    old = (dec.cos, dec.sin)
+    assert old[0].shape[0] == 512 and not dec._old_rope
+    dec.forward(codes)
+    assert dec.cos.shape[0] >= 520 and dec.cos is not old[0]
+    assert any(c is old[0] and s is old[1] for c, s in dec._old_rope)
+    slot2, after = run()
+    assert slot2 is slot and sorted(slot.graphs) == [(2, False), (2, True)]
+    assert torch.equal(after, before)
+    assert after.shape[1] == 1920 * 6 - 555
+    torch.testing.assert_close(after, dec.forward(codes[:, :6])[:, :after.shape[1]], atol=2e-5, rtol=0)
+
+
 @pytest.mark.parametrize("fname,preset", [("codec_tiny.npz", "tiny-customvoice"), ("codec_full.npz", "1.7b-customvoice"),
                                            ("codec_full_chunks.npz", "1.7b-customvoice")])
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
